@@ -19,11 +19,16 @@ batched every --gather-every steps on a side stream.
 
 Output: one JSON line on rank 0 (see README / the driver contract), with
   roofline     -- algorithmic HBM bytes per step / ms_per_step against the 8 TB/s HBM3E peak, plus -- as
-                  short numeric fields, measured in the same run behind the timed region -- the same
-                  region under the library's default fences, without episode ends, 400 steps long,
+                  short numeric fields, measured in the same run behind the timed region (--full only) -- the
+                  same region under the library's default fences, without episode ends, 400 steps long,
                   unstaged, with a forced one-rank exchange, and C5 / the observation variants
-  cpu_baseline -- the oracle (plain-C restatement, OpenMP over envs) timed on this host on a bounded
-                  sample of the same workload, and the bit-for-bit replay of the timed run on it.
+  cpu_baseline -- (--full only) the oracle (plain-C restatement, OpenMP over envs) timed on this host on a
+                  bounded sample of the same workload, and the bit-for-bit replay of the timed run on it.
+
+A plain run sets up, warms up, times the --steps steps and prints the line.  --full adds everything else the
+line can carry: the CPU baseline and its replay, the stream-path leg, the rollout, observation, wrapper,
+C2 / C4 / C5 and variant figures, and the copy ceilings (--cpu-baseline, --stream-leg, --rollout and --extras
+switch single legs of it off).  --dump-outputs DIR writes what the last timed step computed (dump_outputs).
 """
 import argparse
 import json
@@ -253,6 +258,26 @@ def gather_window(requested, steps):
     return max(1, min(int(requested), int(steps)))     # (any `every` <= steps consecutive steps hold a step = every-1 mod every)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, suffix=""):
+    """--dump-outputs: write `arrays` ({name: numpy array with one row per env}) as out_dir/<name><suffix>.npy, float32
+    where that holds every value exactly (float32, 8- and 16-bit integers), float64 otherwise.  Past DUMP_LIMIT_BYTES
+    in all, every array keeps the same fixed, seeded sample of env rows, written as env_index<suffix>.npy."""
+    conv = {k: a.astype(np.float32 if (a.dtype == np.float32 or a.dtype.itemsize <= 2) else np.float64)
+            for k, a in arrays.items()}
+    n = len(next(iter(conv.values())))
+    per_row = sum(a.nbytes for a in conv.values()) // max(1, n) + 8
+    if per_row * n > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // per_row, replace=False))
+        conv = {k: a[rows] for k, a in conv.items()}
+        conv["env_index"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in conv.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), np.ascontiguousarray(a))
+
+
 DEFAULT_QUEUES = "4"       # slices on AQL queues by default (0: HIP-stream slices); see DESIGN 4.1c
 
 
@@ -293,18 +318,31 @@ def main():
                          "region opens with slhip_queues_go (one doorbell per queue), as a captured hipGraph would be launched; "
                          "0 = everything is enqueued inside the region (roofline.unstaged_us either way)")
     ap.add_argument("--stream-leg", type=int, default=1,
-                    help="queue stepping only: 1 = also run K steps of the same kernel through the stream slices under HIP "
-                         "events (roofline.stream_leg_*); 0 = leave it out (profiling runs: only the queues' launches in the trace)")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+                    help="--full, queue stepping only: 1 = also run K steps of the same kernel through the stream slices "
+                         "under HIP events (roofline.stream_leg_*); 0 = leave it out (profiling runs: only the queues' "
+                         "launches in the trace)")
+    ap.add_argument("--cpu-baseline", type=int, default=1,
+                    help="--full: 1 = also time the CPU oracle on the same workload and replay the timed run on it")
     ap.add_argument("--cpu-steps", type=int, default=1001)
     ap.add_argument("--rollout", type=int, default=32,
-                    help="T>0: additionally time T-step fused rollouts (reported under 'extra')")
+                    help="--full: T>0 = additionally time T-step fused rollouts (reported under 'extra')")
     ap.add_argument("--extras", type=int, default=1,
-                    help="1: also time the step with observations (reported under 'extra'; 1 GPU only)")
+                    help="--full: 1 = also time the step with observations, wrappers, the other configs and the "
+                         "region's variants (reported under 'extra' and 'roofline'; 1 GPU only)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline figure too (the legs above); without it the run "
+                         "sets up, warms up, times the --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MiB; see dump_outputs)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: gloo process group and a stand-in step (checks the launcher, the partition, the "
                          "gather windows and the JSON line)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:       # a plain run: the headline figure only
+        args.cpu_baseline = args.extras = args.rollout = args.stream_leg = 0
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
     if args.dry_run:
@@ -561,6 +599,23 @@ def main():
                      "host_enqueue_ms_per_step": float(v[2]), "gather_exposed_ms": float(v[3]) * 1e3}
                     for r, v in enumerate(allr)]
         elapsed = max(float(v[0]) for v in allr)
+
+    if args.dump_outputs:
+        # what the last timed step handed its caller -- its step records (and observation, with --obs) -- and the boards
+        # it left, read before anything else steps this env
+        if gather.collective:       # the records went to that step's slot of a gather window (8-byte records)
+            tt = P + W + K - 1 + shift
+            rec = gather.buf[(tt // gather.every) % 2][tt % gather.every]
+            flags = rec[:, 1:2].contiguous().view(torch.uint8).cpu().numpy()
+            outs = {"reward": rec[:, 0].view(torch.float32).cpu().numpy(), "done": flags[:, 0], "success": flags[:, 1],
+                    "times_up": flags[:, 2]}
+        else:
+            outs = {"reward": env.numpy("reward"), "done": env.numpy("done")}
+            outs.update((k, v.cpu().numpy()) for k, v in env.info.items())
+        outs["board"] = env.numpy("board")
+        if env.obs is not None:
+            outs["obs"] = env.numpy("obs")
+        dump_outputs(args.dump_outputs, outs, "_rank%d" % rank if world > 1 else "")
 
     parity = None
     if args.cpu_baseline and world == 1:
@@ -1264,7 +1319,9 @@ def main():
                          stream_key + "_note": ("HIP events over %d steps of the SAME kernel issued through the %d stream "
                                                 "slice(s) right after the timed region (wall %.5f ms per step)"
                                                 % (K, env.slices, stream_wall_ms))
-                         if stream_wall_ms is not None else "HIP events over the timed region (slice 0's stream)",
+                         if stream_wall_ms is not None else
+                         "wall clock of the timed region (no stream leg in this run; --full runs it)" if use_queues else
+                         "HIP events over the timed region (slice 0's stream)",
                          stream_key + "_achieved": achieved_device, stream_key + "_frac": achieved_device / HBM_PEAK_GBS,
                          "host_enqueue_ms_per_step": (t_enqueued - t_start) / K * 1e3,
                          # the same region under other launchers / regimes / lengths, measured in this run behind the

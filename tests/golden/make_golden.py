@@ -92,6 +92,30 @@ def random_board(rng, h, w, kind):
     return rng.integers(0, 65536, (h, w)).astype(np.uint16)
 
 
+# ------------------------------------------------ differential cases
+
+def gen_ref_differential(R, out):
+    """The cases of tests/test_oracle_golden.py::test_against_compiled_reference with the reference's answers:
+    boards of random shapes and kinds through advance_board (generator PCG64(case), its state after) and
+    alive_counts, so that the test runs where oracle/_ref cannot be built."""
+    from tests import util
+    sp = R.speedups
+    rng = np.random.default_rng(2)
+    rec = {"n": np.array(150)}
+    for k in range(150):
+        h, w = (25, 25) if k % 3 == 0 else tuple(int(v) for v in rng.integers(3, 40, 2))
+        board = util.random_boards(rng, 1, h, w, kind=k % 3)[0]
+        n, p = int(rng.integers(1, 5)), float(rng.choice([0.3, 0.0, 1.0, 0.1]))
+        g = np.random.PCG64(k)
+        sp.set_bit_generator(g)
+        rec["board_%03d" % k], rec["p_n_%03d" % k] = board, np.array([p, n])
+        rec["adv_%03d" % k], rec["rng_%03d" % k] = sp.advance_board(board, p, n), words(g)
+        goals = (rng.integers(0, 8, (h, w)) << 9).astype(np.uint16)
+        rec["goals_%03d" % k], rec["cnt_%03d" % k] = goals, sp.alive_counts(board, goals)
+    np.savez_compressed(os.path.join(out, "ref_differential.npz"), **rec)
+    print("ref_differential: %d cases" % 150)
+
+
 # ----------------------------------------------------------------- primitives
 
 def gen_primitives(R, out):
@@ -860,9 +884,11 @@ def main():
     args = ap.parse_args()
     R = import_reference()
     out = HERE
-    todo = args.only.split(",") if args.only else ["primitives", "patterns", "traces", "wrappers", "pools", "side"]
+    todo = args.only.split(",") if args.only else ["primitives", "refdiff", "patterns", "traces", "wrappers", "pools", "side"]
     if "primitives" in todo:
         gen_primitives(R, out)
+    if "refdiff" in todo:
+        gen_ref_differential(R, out)
     if "patterns" in todo:
         gen_patterns(R, out)
     if "traces" in todo:

@@ -112,21 +112,27 @@ def test_reference_timing_harness():
 
 
 def test_against_compiled_reference():
-    """Random differential test against oracle/_ref (the reference C built from its own sources)."""
+    """Random differential test against the reference C built from its own sources: its answers for the 150 random
+    cases are stored in tests/golden/ref_differential.npz (make_golden.py --only refdiff), and oracle/_ref, where it
+    is built, is asked again."""
     ref = oracle.load_ref()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (reference checkout absent)")
-    rng = np.random.default_rng(2)
+    with np.load(os.path.join(util.GOLDEN, "ref_differential.npz")) as d:
+        cases = {k: d[k] for k in d.files}
+    assert int(cases["n"]) == 150
     for trial in range(150):
-        h, w = (25, 25) if trial % 3 == 0 else tuple(int(v) for v in rng.integers(3, 40, 2))
-        board = util.random_boards(rng, 1, h, w, kind=trial % 3)[0]
-        n, p = int(rng.integers(1, 5)), float(rng.choice([0.3, 0.0, 1.0, 0.1]))
-        g1, g2 = np.random.PCG64(trial), np.random.PCG64(trial)
-        ref.set_bit_generator(g1)
-        assert np.array_equal(ref.advance_board(board, p, n), oracle.advance_board(board, p, n, bitgen=g2))
-        assert g1.state == g2.state
-        goals = (rng.integers(0, 8, (h, w)) << 9).astype(np.uint16)
-        assert np.array_equal(ref.alive_counts(board, goals), oracle.alive_counts(board, goals))
+        board, goals = cases["board_%03d" % trial], cases["goals_%03d" % trial]
+        p, n = float(cases["p_n_%03d" % trial][0]), int(cases["p_n_%03d" % trial][1])
+        g2 = np.random.PCG64(trial)
+        got = oracle.advance_board(board, p, n, bitgen=g2)
+        assert np.array_equal(got, cases["adv_%03d" % trial]), trial
+        assert np.array_equal(oracle.pcg64_state_words(g2), cases["rng_%03d" % trial]), trial
+        assert np.array_equal(oracle.alive_counts(board, goals), cases["cnt_%03d" % trial]), trial
+        if ref is not None:
+            g1 = np.random.PCG64(trial)
+            ref.set_bit_generator(g1)
+            assert np.array_equal(ref.advance_board(board, p, n), got)
+            assert g1.state == g2.state
+            assert np.array_equal(ref.alive_counts(board, goals), oracle.alive_counts(board, goals))
 
 
 @pytest.mark.parametrize("name", util.trace_names())

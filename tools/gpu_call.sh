@@ -3,8 +3,8 @@
 #   gpurun --timeout 1800 -- bash tools/gpu_call.sh <tag> <task> [<task> ...]
 # Results land in gpurun_out/<tag>_<task>.txt.  Tasks:
 #   suite            python -m pytest tests -m gpu -x -q
-#   bench20          the driver's command (python bench.py --steps 20 --warmup 5), one line of the numbers that matter
-#   bench400         python bench.py --steps 400 --warmup 40 --extras 0 --rollout 0
+#   bench20          python bench.py --full --steps 20 --warmup 5, one line of the numbers that matter
+#   bench400         python bench.py --full --steps 400 --warmup 40 --extras 0 --rollout 0
 #   kfit[:spread]    region-length fit, tools/exp/kfit.py <spread> none 5   (fixed cost + per-step cost of a timed region)
 #   trace[:args]     kernel-clock timeline on a -DSL_TRACE build (tools/ab_build.sh trace -DSL_TRACE -DSL_DEV_SHAPES first):
 #                    tools/trace_overlap.py 12 --queues 4 --fences none <args>
@@ -28,8 +28,8 @@ for task in "$@"; do
   out=$O/${TAG}_${name}.txt
   case $name in
     suite)    ( timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -5 ) > $out ;;
-    bench20)  timeout 900 python bench.py --steps 20 --warmup 5 2>$O/${TAG}_bench20.err | tail -1 > $O/${TAG}_bench20.json; summ $O/${TAG}_bench20.json > $out ;;
-    bench400) timeout 600 python bench.py --steps 400 --warmup 40 --extras 0 --rollout 0 2>/dev/null | tail -1 > $O/${TAG}_bench400.json; summ $O/${TAG}_bench400.json > $out ;;
+    bench20)  timeout 900 python bench.py --full --steps 20 --warmup 5 2>$O/${TAG}_bench20.err | tail -1 > $O/${TAG}_bench20.json; summ $O/${TAG}_bench20.json > $out ;;
+    bench400) timeout 600 python bench.py --full --steps 400 --warmup 40 --extras 0 --rollout 0 2>/dev/null | tail -1 > $O/${TAG}_bench400.json; summ $O/${TAG}_bench400.json > $out ;;
     kfit)     timeout 300 python tools/exp/kfit.py ${arg:-1} none 5 2>&1 | grep -v amdgpu.ids > $out ;;
     trace)    SAFELIFE_HIP_LIB=$PWD/tools/lib_trace.so SAFELIFE_HIP_LIB_ANY_ABI=1 timeout 300 python tools/trace_overlap.py 12 --queues 4 --fences none $arg 2>&1 | grep -v amdgpu.ids > $out ;;
     prof)     bash tools/prof_run.sh $TAG > /dev/null 2>&1; head -4 $O/${TAG}_kernel_trace.txt > $out; grep -E "FETCH_SIZE|WRITE_SIZE" $O/${TAG}_pmc.txt >> $out ;;
