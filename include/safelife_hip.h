@@ -542,8 +542,9 @@ int slhip_env_obs(const sl_env_batch *env, void *stream);
  * the level pool, the points tables and the view; of sl_env_scalars only num_steps, level_idx, episode_idx, spawn_prob,
  * goals_static and loaded are used (the per-agent words live in `agents`).  env->obs and env->out are ignored: the
  * per-agent outputs are `multi`'s.  An env whose agents are ALL done reloads its next pool level inside the step when
- * env->auto_reset is set (training/base_algo.py:231-236 resets on np.all(done)); wrappers, the finished-episode queue
- * and the policy layout are single-agent features (SL_E_UNSUPPORTED). */
+ * env->auto_reset is set (training/base_algo.py:231-236 resets on np.all(done)).  These two entry points refuse
+ * wrappers, the finished-episode queue and the policy layout (SL_E_UNSUPPORTED): the _ex pair below takes them, with
+ * the per-agent buffers they need in sl_multi_extras. */
 typedef struct sl_agent_state {   /* per env and agent (48 bytes) */
     int32_t row, col;             /* where the agent is -- or was when it left the board (GameState.agent_locs) */
     int32_t old_value;            /* SafeLifeEnv._old_game_value[a] */
@@ -571,6 +572,45 @@ typedef struct sl_multi_agent {
 int slhip_env_step_multi(const sl_env_batch *env, const sl_multi_agent *multi, const int32_t *actions, void *stream);
 /* SafeLifeEnv.reset() for the envs with mask[e] != 0 (NULL: all), as slhip_env_reset. */
 int slhip_env_reset_multi(const sl_env_batch *env, const sl_multi_agent *multi, const uint8_t *mask, void *stream);
+
+/* ---- multi-agent batches with the training wrappers, the finished-episode queue and the policy layout ----------------
+ * The reference's multi-agent training stack: SafeLifeEnv(single_agent=False) under MovementBonusWrapper(as_penalty),
+ * ExtraExitBonus, SimpleSideEffectPenalty and MinPerformanceScheduler (training/env_factory.py:277-283), and the
+ * episode-end side-effect pass of safelife_env.py:183-192.  env->wrap configures the wrappers as for single-agent
+ * batches (flags, coefficients, move_table, inaction_board / inaction_rng; wrap.state, wrap.shaped_reward and
+ * wrap.pool_baseline are not used: the per-agent buffers are below).  What differs per agent:
+ *   - the shaped reward is float32 per agent: the reference's reward is a float32 array that every wrapper updates in
+ *     place, so each wrapper rounds once -- f32(f64(r) + movement term), then r - f32(move_bonus) (as_penalty), then
+ *     f32(f64(r) + done * exit_bonus * episode_reward) unless times_up, then f32(f64(r) - delta * penalty_coef);
+ *   - an agent that is done keeps being shaped until the env resets (its done flag stays set, its location stays put);
+ *   - one side-effect count per env, against the board as the multi-agent reset leaves it (every agent's cell carries
+ *     the EXIT bit iff THAT agent could leave: `baseline` below) or the inaction board, subtracted from every agent;
+ *     CellTypes.player does not clear colour or exit bits, so a coloured agent that moves counts at both cells.
+ * An episode is queued (env->finished) once, on the step where every agent is done and at least one was active before
+ * it: one sl_episode_record (agent 0's accumulators, success and times_up in its own fields) plus one sl_step_out per
+ * agent in `finished_agents`, and the board as the agents left it; slhip_side_effects consumes the queue as it does
+ * a single-agent one (env->H x W must be a row-kernel board shape). */
+typedef struct sl_multi_extras {
+    sl_wrap_state *wrap_state;    /* [B, A]: each agent's MovementBonusWrapper trail; last_side_effect (the env's count,
+                                     the same in every agent's record); reserved[0] = can_exit() of the agent at reset */
+    float *shaped_reward;         /* [B, A] out: what the outermost wrapper's step() returns, per agent */
+    uint16_t *baseline;           /* workspace [L, H, W]: every pool level as the multi-agent reset leaves it (the
+                                     starting-state baseline); written by slhip_env_reset_multi_ex, read by the step.
+                                     Needed with SL_WRAP_SIDE_EFFECT */
+    sl_step_out *finished_agents; /* [env->finished.capacity, A]: each agent's record of the step that queued an entry */
+    void *policy_obs;             /* [B, A, C, view_w, view_h] uint8 or float32 (policy_dtype): sl_env_batch.policy_obs
+                                     per agent; NULL = skip.  env->policy_obs must be NULL */
+    int32_t policy_dtype;         /* 0 = uint8, 1 = float32 */
+    int32_t reserved;
+} sl_multi_extras;
+/* slhip_env_step_multi with env->wrap, env->finished and extras.  An inaction baseline advances in a launch of its own
+ * in front of the step. */
+int slhip_env_step_multi_ex(const sl_env_batch *env, const sl_multi_agent *multi, const sl_multi_extras *extras,
+                            const int32_t *actions, void *stream);
+/* slhip_env_reset_multi, and the wrappers' reset(); also (re)writes extras->baseline for every pool level.  Call it
+ * before the first step. */
+int slhip_env_reset_multi_ex(const sl_env_batch *env, const sl_multi_agent *multi, const sl_multi_extras *extras,
+                             const uint8_t *mask, void *stream);
 
 /* The raw uint32 view (output_channels=None, safelife_env.py:141) -> the tensor the policy network
  * convolves: channel-first with the spatial axes swapped, out[b][c][x][y] = (view[b][y][x] >> channels[c]) & 1,

@@ -22,7 +22,7 @@ EXPORTS = (
     "slhip_advance_board", "slhip_advance_board_each", "slhip_life_occupancy", "slhip_alive_counts", "slhip_execute_actions",
     "slhip_env_prepare", "slhip_pool_baseline", "slhip_pool_write", "slhip_goal_cache_bytes", "slhip_env_reset", "slhip_env_step", "slhip_env_step_slices", "slhip_env_step_range", "slhip_env_rollout",
     "slhip_streams_concurrent", "slhip_streams_order",
-    "slhip_env_obs", "slhip_env_step_multi", "slhip_env_reset_multi",
+    "slhip_env_obs", "slhip_env_step_multi", "slhip_env_reset_multi", "slhip_env_step_multi_ex", "slhip_env_reset_multi_ex",
     "slhip_obs_to_policy", "slhip_sample_actions", "slhip_side_effects",
     "slhip_gather_unique_id", "slhip_gather_init", "slhip_gather_window", "slhip_gather_destroy",
     "slhip_gather_window_async", "slhip_gather_done", "slhip_gather_wait_streams",
@@ -125,6 +125,13 @@ class MultiAgent(C.Structure):
                 ("out", C.c_void_p), ("obs", C.c_void_p)]
 
 
+class MultiExtras(C.Structure):
+    """struct sl_multi_extras"""
+    _fields_ = [("wrap_state", C.c_void_p), ("shaped_reward", C.c_void_p), ("baseline", C.c_void_p),
+                ("finished_agents", C.c_void_p), ("policy_obs", C.c_void_p), ("policy_dtype", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class EnvBatch(C.Structure):
     _fields_ = (
         [(n, C.c_int32) for n in ENV_SCALARS_HEAD]
@@ -183,6 +190,9 @@ def lib():
         if hasattr(L, "slhip_env_step_multi"):
             L.slhip_env_step_multi.argtypes = [C.POINTER(EnvBatch), C.POINTER(MultiAgent), _p, _p]
             L.slhip_env_reset_multi.argtypes = [C.POINTER(EnvBatch), C.POINTER(MultiAgent), _p, _p]
+        if hasattr(L, "slhip_env_step_multi_ex"):
+            L.slhip_env_step_multi_ex.argtypes = [C.POINTER(EnvBatch), C.POINTER(MultiAgent), C.POINTER(MultiExtras), _p, _p]
+            L.slhip_env_reset_multi_ex.argtypes = [C.POINTER(EnvBatch), C.POINTER(MultiAgent), C.POINTER(MultiExtras), _p, _p]
         if hasattr(L, "slhip_queues_step"):
             L.slhip_queues_open.argtypes = [C.POINTER(EnvBatch), C.c_int, _p, C.c_int, C.POINTER(C.c_void_p)]
             L.slhip_queues_step.argtypes = [C.c_void_p, C.POINTER(EnvBatch), _p, C.c_int]

@@ -1475,6 +1475,62 @@ int slhip_env_reset_multi(const sl_env_batch *env, const sl_multi_agent *multi, 
     return err == hipSuccess ? SL_OK : hip_fail(err, "env_reset_multi launch");
 }
 
+// The _ex pair: check_multi without the refusal, plus what the wrappers, the queue and the policy layout need per agent.
+static int check_multi_ex(const sl_env_batch *env, const sl_multi_agent *m, const sl_multi_extras *x) {
+    int rc = check_env(env);
+    if (rc) return rc;
+    if (!m || !x) return fail(SL_E_ARG, "null multi-agent description or extras");
+    if (m->n_agents < 1 || m->n_agents > SL_MAX_AGENTS) return fail(SL_E_ARG, "n_agents outside 1..SL_MAX_AGENTS");
+    if (!m->agents || !m->pool_agents || !m->out) return fail(SL_E_ARG, "null pointer in sl_multi_agent");
+    if (env->policy_obs) return fail(SL_E_ARG, "env->policy_obs must be null: the per-agent layout is extras->policy_obs");
+    if (x->policy_obs && (env->n_channels < 1 || (x->policy_dtype != 0 && x->policy_dtype != 1)))
+        return fail(SL_E_ARG, "extras->policy_obs needs n_channels >= 1 and policy_dtype 0 (uint8) or 1 (float32)");
+    if (env->wrap.flags && !x->wrap_state) return fail(SL_E_ARG, "extras->wrap_state is null");
+    if (env->wrap.flags && !x->shaped_reward) return fail(SL_E_ARG, "extras->shaped_reward is null");
+    if ((env->wrap.flags & SL_WRAP_SIDE_EFFECT) && !x->baseline) return fail(SL_E_ARG, "extras->baseline is null");
+    if (env->finished.capacity > 0 && !x->finished_agents) return fail(SL_E_ARG, "extras->finished_agents is null");
+    return SL_OK;
+}
+
+// the kernels' view of the batch: the per-agent policy tensor in the slot of the single-agent one
+static sl_env_batch multi_ex_view(const sl_env_batch &env, const sl_multi_extras &x) {
+    sl_env_batch v = env;
+    v.policy_obs = x.policy_obs;
+    v.policy_dtype = x.policy_dtype;
+    v.obs = nullptr;            // (the per-agent observation is sl_multi_agent.obs)
+    return v;
+}
+
+int slhip_env_step_multi_ex(const sl_env_batch *env, const sl_multi_agent *multi, const sl_multi_extras *extras,
+                            const int32_t *actions, void *stream) {
+    int rc = check_multi_ex(env, multi, extras);
+    if (rc) return rc;
+    if (!actions) return fail(SL_E_ARG, "null actions");
+    if (env->B == 0) return SL_OK;
+    const sl::Jump *jump;
+    if ((rc = jump_table(&jump))) return rc;
+    const sl_env_batch v = multi_ex_view(*env, *extras);
+    hipError_t err = drop_goal_cache(env, (hipStream_t)stream);
+    // env_wrappers.py:179-180: the inaction baseline advances once per step, ahead of the step that compares against it
+    if (err == hipSuccess && (env->wrap.flags & SL_WRAP_INACTION))
+        err = sl::launch_inaction_generic(v, jump, (hipStream_t)stream);
+    if (err == hipSuccess) err = sl::launch_env_step_multi(v, *multi, actions, jump, (hipStream_t)stream, extras);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "env_step_multi_ex launch");
+}
+
+int slhip_env_reset_multi_ex(const sl_env_batch *env, const sl_multi_agent *multi, const sl_multi_extras *extras,
+                             const uint8_t *mask, void *stream) {
+    int rc = check_multi_ex(env, multi, extras);
+    if (rc) return rc;
+    if (env->B == 0) return SL_OK;
+    const sl_env_batch v = multi_ex_view(*env, *extras);
+    hipError_t err = drop_goal_cache(env, (hipStream_t)stream);
+    if (err == hipSuccess && extras->baseline)
+        err = sl::launch_multi_baseline(v, *multi, extras->baseline, (hipStream_t)stream);
+    if (err == hipSuccess) err = sl::launch_env_reset_multi(v, *multi, mask, (hipStream_t)stream, extras);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "env_reset_multi_ex launch");
+}
+
 int slhip_env_obs(const sl_env_batch *env, void *stream) {
     int rc = check_env(env);
     if (rc) return rc;

@@ -256,6 +256,35 @@ __device__ __forceinline__ int side_effect_cell(u32 b, u32 b0, u32 goal, bool ig
 // first, in float64 with the reference's operation order (env_wrappers.py:67-92,124-128,210-213).
 // `side_effect` is the count of differing cells (ignored without SL_WRAP_SIDE_EFFECT).
 // MT: anything indexable that yields the movement table's doubles (global or LDS pointer).
+// MovementBonusWrapper's distance term (env_wrappers.py:67-80) for the agent now at (ly, lx), and the append of that
+// location to its trail: the index into the movement table.
+__device__ __forceinline__ int wrap_move_distance(const sl_wrappers &w, sl_wrap_state &st, int ly, int lx) {
+    const int per = w.move_period;
+    int np_ = st.n_prior;
+    int d = 0;                                      // no agent: speed = sum(empty) = 0
+    if (ly >= 0) {
+        const int dr = ly - st.prior[0][0], dc = lx - st.prior[0][1];
+        d = (dr < 0 ? -dr : dr) + (dc < 0 ? -dc : dc);
+        if (np_ < per) d += per - np_;              // "as if it had been moving before entering"
+    }
+    if (np_ >= per) {                               // deque(maxlen=per).append
+#pragma unroll
+        for (int k = 0; k + 1 < SL_WRAP_MAX_PERIOD; ++k) {
+            st.prior[k][0] = st.prior[k + 1][0];
+            st.prior[k][1] = st.prior[k + 1][1];
+        }
+        np_ = per - 1;
+    }
+#pragma unroll
+    for (int k = 0; k < SL_WRAP_MAX_PERIOD; ++k)
+        if (k == np_) {
+            st.prior[k][0] = (int16_t)ly;
+            st.prior[k][1] = (int16_t)lx;
+        }
+    st.n_prior = np_ + 1;
+    return d;
+}
+
 template <typename MT>
 __device__ __forceinline__ double wrap_step(const sl_wrappers &w, sl_wrap_state &st, MT move_table, float reward,
                                             bool done, bool times_up, float episode_reward, int ly, int lx,
@@ -263,37 +292,38 @@ __device__ __forceinline__ double wrap_step(const sl_wrappers &w, sl_wrap_state 
 #pragma clang fp contract(off)      // numpy rounds the product and the sum separately: no fused multiply-add
     double r = (double)reward;
     if (w.flags & SL_WRAP_MOVEMENT) {
-        const int per = w.move_period;
-        int np_ = st.n_prior;
-        int d = 0;                                      // no agent: speed = sum(empty) = 0
-        if (ly >= 0) {
-            const int dr = ly - st.prior[0][0], dc = lx - st.prior[0][1];
-            d = (dr < 0 ? -dr : dr) + (dc < 0 ? -dc : dc);
-            if (np_ < per) d += per - np_;              // "as if it had been moving before entering"
-        }
-        r = r + move_table[d];
+        r = r + move_table[wrap_move_distance(w, st, ly, lx)];
         if (w.flags & SL_WRAP_AS_PENALTY) r = r - w.move_bonus;
-        if (np_ >= per) {                               // deque(maxlen=per).append
-#pragma unroll
-            for (int k = 0; k + 1 < SL_WRAP_MAX_PERIOD; ++k) {
-                st.prior[k][0] = st.prior[k + 1][0];
-                st.prior[k][1] = st.prior[k + 1][1];
-            }
-            np_ = per - 1;
-        }
-#pragma unroll
-        for (int k = 0; k < SL_WRAP_MAX_PERIOD; ++k)
-            if (k == np_) {
-                st.prior[k][0] = (int16_t)ly;
-                st.prior[k][1] = (int16_t)lx;
-            }
-        st.n_prior = np_ + 1;
     }
     if ((w.flags & SL_WRAP_EXIT_BONUS) && !times_up)
         r = r + (done ? 1.0 : 0.0) * w.exit_bonus * (double)episode_reward;
     if (w.flags & SL_WRAP_SIDE_EFFECT) {
         const int delta = side_effect - st.last_side_effect;
         r = r - (double)delta * w.penalty_coef;
+        st.last_side_effect = side_effect;
+    }
+    return r;
+}
+
+// The same wrappers over ONE AGENT of a multi-agent env (include/safelife_hip.h, sl_multi_extras): the reference's
+// reward is a float32 array updated in place by every wrapper, so each wrapper's result is rounded to float32.  numpy
+// evaluates `reward += bonus * speed**power` and `reward += done * bonus * episode_reward` in float64 (float64 right-hand
+// sides), `reward -= movement_bonus` in float32 (a Python float takes the array's type) and `reward -= delta * coef` in
+// float64 (a numpy float64 scalar).
+__device__ __forceinline__ float wrap_step_multi(const sl_wrappers &w, sl_wrap_state &st, const double *move_table,
+                                                 float reward, bool done, bool times_up, float episode_reward, int ly,
+                                                 int lx, int side_effect) {
+#pragma clang fp contract(off)
+    float r = reward;
+    if (w.flags & SL_WRAP_MOVEMENT) {
+        r = (float)((double)r + move_table[wrap_move_distance(w, st, ly, lx)]);
+        if (w.flags & SL_WRAP_AS_PENALTY) r = r - (float)w.move_bonus;
+    }
+    if ((w.flags & SL_WRAP_EXIT_BONUS) && !times_up)
+        r = (float)((double)r + (done ? 1.0 : 0.0) * w.exit_bonus * (double)episode_reward);
+    if (w.flags & SL_WRAP_SIDE_EFFECT) {
+        const int delta = side_effect - st.last_side_effect;
+        r = (float)((double)r - (double)delta * w.penalty_coef);
         st.last_side_effect = side_effect;
     }
     return r;

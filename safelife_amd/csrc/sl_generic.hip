@@ -303,7 +303,7 @@ __device__ void write_obs(const sl_env_batch &env, int e, const u16 *board, cons
                 for (int c = 0; c < C; ++c) o[c] = (word >> env.channels[c]) & 1u;
             }
         }
-        if (env.policy_obs && slot < 0) {        // channel-first, spatial axes swapped: [C, vw, vh] (training/models.py:100-103)
+        if (env.policy_obs) {       // channel-first, spatial axes swapped: [C, vw, vh] (training/models.py:100-103)
             const size_t base = (size_t)e * C * nv + (size_t)vx * vh + vy;
             for (int c = 0; c < C; ++c) {
                 const u32 bit = (word >> env.channels[c]) & 1u;
@@ -609,6 +609,18 @@ __device__ bool recolor_exits_multi(u16 *board, int W, const int *loc, const int
     return any_can;
 }
 
+// The wrappers' reset() for the agents of env e (sl_multi_extras), after reset_block_multi: each agent's trail starts
+// where it stands; reserved[0] keeps whether it could leave at reset (its cell's EXIT bit).
+__device__ __forceinline__ void wrap_reset_multi(const sl_env_batch &env, const sl_multi_extras &x, int e, int A,
+                                                 const u16 *brd, const int *loc) {
+    const int tid = threadIdx.x;
+    if (env.wrap.flags && tid < A) {
+        sl_wrap_state &st = x.wrap_state[(size_t)e * A + tid];
+        wrap_reset(st, loc[2 * tid], loc[2 * tid + 1]);
+        st.reserved[0] = (brd[loc[2 * tid] * env.W + loc[2 * tid + 1]] & EXIT) ? 1 : 0;
+    }
+}
+
 // SafeLifeEnv.reset() body of a multi-agent env: pool level -> LDS board and the per-env / per-agent state.
 __device__ void reset_block_multi(const sl_env_batch &env, const sl_multi_agent &m, int e, u16 *brd, MultiLds ml, int *wave_tot) {
     const int HW = env.H * env.W, tid = threadIdx.x, E = env.E, A = m.n_agents;
@@ -681,7 +693,9 @@ __device__ void reset_block_multi(const sl_env_batch &env, const sl_multi_agent 
     __syncthreads();
 }
 
-__global__ __launch_bounds__(GB_MAX) void k_env_step_multi(sl_env_batch env, sl_multi_agent m,
+// EX: the training wrappers, the finished-episode queue and the policy layout (slhip_env_step_multi_ex)
+template <bool EX>
+__global__ __launch_bounds__(GB_MAX) void k_env_step_multi(sl_env_batch env, sl_multi_agent m, sl_multi_extras x,
                                                        const int32_t *__restrict__ actions,
                                                        const Jump *__restrict__ jump) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -740,7 +754,7 @@ __global__ __launch_bounds__(GB_MAX) void k_env_step_multi(sl_env_batch env, sl_
         const int steps = sc->num_steps + 1;
         sc->num_steps = steps;
         const bool times_up = steps >= env.time_limit;
-        bool all_done = true;
+        bool all_done = true, any_active = false;
         for (int a = 0; a < A; ++a) {
             const u32 cell = nxt[ml.loc[2 * a] * W + ml.loc[2 * a + 1]];
             const bool success = has_exited(cell);
@@ -764,12 +778,77 @@ __global__ __launch_bounds__(GB_MAX) void k_env_step_multi(sl_env_batch env, sl_
             ag[a].episode_length = o.episode_length;
             ag[a].is_active = (active && !done) ? 1 : 0;
             all_done = all_done && done;
+            any_active = any_active || active;
         }
         sc->agent_row = ml.loc[0];
         sc->agent_col = ml.loc[1];
         ml.flag[0] = all_done ? 1 : 0;
+        if (EX) ml.flag[1] = any_active ? 1 : 0;
     }
     __syncthreads();
+    if (EX) {
+        // the step on which every agent is done ends the env's episode: queue it for the side-effect pass
+        // (safelife_env.py:183-192 scores it once, when np.all(done) first holds), with every agent's record
+        if (tid == 0) {
+            int slot = -1;
+            if (env.finished.capacity > 0 && ml.flag[0] && ml.flag[1]) {
+                slot = atomicAdd(env.finished.count, 1);
+                if (slot < env.finished.capacity) {
+                    const sl_step_out o0 = m.out[(size_t)e * A];
+                    sl_episode_record rec;
+                    rec.env = e + env.finished.env_base;
+                    rec.level = sc->level_idx;
+                    rec.num_steps = sc->num_steps;
+                    rec.episode_idx = sc->episode_idx;
+                    rec.spawn_prob = sc->spawn_prob;
+                    rec.episode_reward = o0.episode_reward;
+                    rec.episode_length = o0.episode_length;
+                    rec.success = o0.success;
+                    rec.times_up = o0.times_up;
+                    rec.n_cell_types = rec.reserved = 0;
+                    env.finished.records[slot] = rec;
+                    for (int a = 0; a < A; ++a) x.finished_agents[(size_t)slot * A + a] = m.out[(size_t)e * A + a];
+                } else {
+                    slot = -1;
+                }
+            }
+            ml.flag[2] = slot;
+        }
+        __syncthreads();
+        if (ml.flag[2] >= 0) {      // the board as the agents left it, before any reload
+            u16 *dst = env.finished.boards + (size_t)ml.flag[2] * HW;
+            for (int i = tid; i < HW; i += GB) dst[i] = nxt[i];
+        }
+        if (env.wrap.flags) {       // env_wrappers.py over every agent: movement bonus, exit bonus, side-effect penalty
+            int side = 0;
+            if (env.wrap.flags & SL_WRAP_SIDE_EFFECT) {
+                // one count per env; exit cells never count (env_wrappers.py:191-193): flag them in the free `rows` buffer
+                for (int i = tid; i < HW; i += GB) rows[i] = 0;
+                __syncthreads();
+                for (int k = tid; k < E; k += GB)
+                    if (exits[k] >= 0) rows[exits[k]] = 1;
+                __syncthreads();
+                // "starting-state": the level as the multi-agent reset left it; "inaction": the board k_inaction_generic
+                // advanced just before this launch
+                const u16 *b0 = (env.wrap.flags & SL_WRAP_INACTION) ? env.wrap.inaction_board + (size_t)e * HW
+                                                                     : x.baseline + (size_t)sc->level_idx * HW;
+                const bool ignore = (env.wrap.flags & SL_WRAP_IGNORE_REWARD_CELLS) != 0;
+                int mine = 0;
+                for (int i = tid; i < HW; i += GB)
+                    if (!rows[i]) mine += side_effect_cell(nxt[i] & 0xFFFFu & ~PLAYER, (u32)b0[i] & ~PLAYER, goals[i], ignore);
+                side = block_sum(mine, l.wave_tot);
+            }
+            if (tid == 0)
+                for (int a = 0; a < A; ++a) {
+                    const sl_step_out o = m.out[(size_t)e * A + a];
+                    x.shaped_reward[(size_t)e * A + a] =
+                        wrap_step_multi(env.wrap, x.wrap_state[(size_t)e * A + a], env.wrap.move_table, o.reward,
+                                        o.done != 0, o.times_up != 0, o.episode_reward, ml.loc[2 * a], ml.loc[2 * a + 1],
+                                        side);
+                }
+            __syncthreads();
+        }
+    }
     u16 *sw = cur;
     cur = nxt;
     nxt = sw;
@@ -780,18 +859,20 @@ __global__ __launch_bounds__(GB_MAX) void k_env_step_multi(sl_env_batch env, sl_
         }
         __syncthreads();
         reset_block_multi(env, m, e, cur, ml, l.wave_tot);
+        if (EX) wrap_reset_multi(env, x, e, A, cur, ml.loc);
         if (tid < 4) l.rng[tid] = ((const u64 *)(env.rng + e))[tid];
         __syncthreads();
     }
     for (int i = tid; i < HW; i += GB) gboard[i] = cur[i];
     if (tid < 4) ((u64 *)(env.rng + e))[tid] = l.rng[tid];
     __syncthreads();   // goals written by this workgroup are read back below
-    if (m.obs)
+    if (m.obs || (EX && env.policy_obs))
         for (int a = 0; a < A; ++a)
             write_obs(env, e, cur, ggoals, ml.loc[2 * a], ml.loc[2 * a + 1], exits, m.obs, e * A + a, ml.stage);
 }
 
-__global__ __launch_bounds__(GB_MAX) void k_env_reset_multi(sl_env_batch env, sl_multi_agent m,
+template <bool EX>
+__global__ __launch_bounds__(GB_MAX) void k_env_reset_multi(sl_env_batch env, sl_multi_agent m, sl_multi_extras x,
                                                         const uint8_t *__restrict__ mask) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int HW = env.H * env.W, e = blockIdx.x, tid = threadIdx.x, A = m.n_agents;
@@ -807,13 +888,51 @@ __global__ __launch_bounds__(GB_MAX) void k_env_reset_multi(sl_env_batch env, sl
     }
     __syncthreads();
     reset_block_multi(env, m, e, l.buf[0], ml, l.wave_tot);
+    if (EX) wrap_reset_multi(env, x, e, A, l.buf[0], ml.loc);
     u16 *gboard = env.board + (size_t)e * HW;
     for (int i = tid; i < HW; i += GB) gboard[i] = l.buf[0][i];
     __syncthreads();
-    if (m.obs)
+    if (m.obs || (EX && env.policy_obs))
         for (int a = 0; a < A; ++a)
             write_obs(env, e, l.buf[0], env.goals + (size_t)e * HW, ml.loc[2 * a], ml.loc[2 * a + 1],
                       env.exit_locs + (size_t)e * env.E, m.obs, e * A + a, ml.stage);
+}
+
+// SimpleSideEffectPenalty's starting-state baseline of every pool level of a multi-agent batch (sl_multi_extras.baseline):
+// the level as reset_block_multi leaves it -- each agent's cell with the EXIT bit iff that agent can leave, the exits
+// painted -- which depends on the level alone.  One workgroup per level.
+__global__ __launch_bounds__(GB_MAX) void k_multi_baseline(sl_env_batch env, sl_multi_agent m, u16 *__restrict__ baseline) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int HW = env.H * env.W, l = blockIdx.x, tid = threadIdx.x, A = m.n_agents;
+    GenericLds g = carve(smem, HW, 4);
+    MultiLds ml = carve_multi(smem, HW, false);
+    u16 *brd = g.buf[0];
+    const sl_level_agent *pa = m.pool_agents + (size_t)l * A;
+    const u16 *pb = env.pool_board + (size_t)l * HW, *pg = env.pool_goals + (size_t)l * HW;
+    for (int i = tid; i < HW; i += GB) brd[i] = pb[i];
+    if (tid < A) {
+        ml.loc[2 * tid] = pa[tid].row;
+        ml.loc[2 * tid + 1] = pa[tid].col;
+    }
+    __syncthreads();
+    for (int a = 0; a < A; ++a) {
+        const int s = board_score(brd, pg, HW, env.points_table + 72 * pa[a].table_idx, g.wave_tot);
+        if (tid == 0) ml.score[a] = s;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        sl_agent_state ag[SL_MAX_AGENTS];
+        int required[SL_MAX_AGENTS];
+        for (int a = 0; a < A; ++a) {
+            ag[a].initial_points = pa[a].initial_points;
+            required[a] = pa[a].required_reset;
+        }
+        recolor_exits_multi(brd, env.W, ml.loc, ml.score, A, ag, required, env.pool_exit_locs + (size_t)l * env.E, env.E,
+                            env.exit_points);
+    }
+    __syncthreads();
+    u16 *dst = baseline + (size_t)l * HW;
+    for (int i = tid; i < HW; i += GB) dst[i] = brd[i];
 }
 
 __global__ __launch_bounds__(GB_MAX) void k_env_reset_generic(sl_env_batch env,
@@ -965,19 +1084,42 @@ hipError_t launch_env_reset_generic(const sl_env_batch &env, const uint8_t *mask
 }
 
 hipError_t launch_env_step_multi(const sl_env_batch &env, const sl_multi_agent &m, const int32_t *actions, const Jump *jump,
-                                 hipStream_t stream) {
+                                 hipStream_t stream, const sl_multi_extras *x) {
     const size_t lds = multi_lds_bytes(env, m);
-    hipError_t err = set_lds((const void *)k_env_step_multi, lds);
+    const void *fn = x ? (const void *)k_env_step_multi<true> : (const void *)k_env_step_multi<false>;
+    hipError_t err = set_lds(fn, lds);
     if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(k_env_step_multi, dim3(env.B), dim3(generic_threads(env.H * env.W)), lds, stream, env, m, actions, jump);
+    const sl_multi_extras none = {};
+    if (x)
+        hipLaunchKernelGGL(k_env_step_multi<true>, dim3(env.B), dim3(generic_threads(env.H * env.W)), lds, stream, env, m, *x,
+                           actions, jump);
+    else
+        hipLaunchKernelGGL(k_env_step_multi<false>, dim3(env.B), dim3(generic_threads(env.H * env.W)), lds, stream, env, m,
+                           none, actions, jump);
     return hipGetLastError();
 }
 
-hipError_t launch_env_reset_multi(const sl_env_batch &env, const sl_multi_agent &m, const uint8_t *mask, hipStream_t stream) {
+hipError_t launch_env_reset_multi(const sl_env_batch &env, const sl_multi_agent &m, const uint8_t *mask, hipStream_t stream,
+                                  const sl_multi_extras *x) {
     const size_t lds = multi_lds_bytes(env, m);
-    hipError_t err = set_lds((const void *)k_env_reset_multi, lds);
+    const void *fn = x ? (const void *)k_env_reset_multi<true> : (const void *)k_env_reset_multi<false>;
+    hipError_t err = set_lds(fn, lds);
     if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(k_env_reset_multi, dim3(env.B), dim3(generic_threads(env.H * env.W)), lds, stream, env, m, mask);
+    const sl_multi_extras none = {};
+    if (x)
+        hipLaunchKernelGGL(k_env_reset_multi<true>, dim3(env.B), dim3(generic_threads(env.H * env.W)), lds, stream, env, m, *x,
+                           mask);
+    else
+        hipLaunchKernelGGL(k_env_reset_multi<false>, dim3(env.B), dim3(generic_threads(env.H * env.W)), lds, stream, env, m,
+                           none, mask);
+    return hipGetLastError();
+}
+
+hipError_t launch_multi_baseline(const sl_env_batch &env, const sl_multi_agent &m, uint16_t *baseline, hipStream_t stream) {
+    const size_t lds = multi_lds_bytes(env, m);
+    hipError_t err = set_lds((const void *)k_multi_baseline, lds);
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL(k_multi_baseline, dim3(env.L), dim3(generic_threads(env.H * env.W)), lds, stream, env, m, baseline);
     return hipGetLastError();
 }
 

@@ -25,9 +25,13 @@ hipError_t launch_env_reset_generic(const sl_env_batch &env, const uint8_t *mask
 hipError_t launch_inaction_generic(const sl_env_batch &env, const Jump *jump, hipStream_t stream);
 hipError_t launch_env_obs_generic(const sl_env_batch &env, hipStream_t stream);
 // multi-agent boards (sl_multi_agent): the fused step / reset, one workgroup per board
+// (x != null: with the wrappers, the finished-episode queue and the policy layout -- the _ex entry points)
 hipError_t launch_env_step_multi(const sl_env_batch &env, const sl_multi_agent &m, const int32_t *actions, const Jump *jump,
-                                 hipStream_t stream);
-hipError_t launch_env_reset_multi(const sl_env_batch &env, const sl_multi_agent &m, const uint8_t *mask, hipStream_t stream);
+                                 hipStream_t stream, const sl_multi_extras *x = nullptr);
+hipError_t launch_env_reset_multi(const sl_env_batch &env, const sl_multi_agent &m, const uint8_t *mask, hipStream_t stream,
+                                  const sl_multi_extras *x = nullptr);
+// every pool level as the multi-agent reset leaves it -> baseline [L,H,W]
+hipError_t launch_multi_baseline(const sl_env_batch &env, const sl_multi_agent &m, uint16_t *baseline, hipStream_t stream);
 struct sl_channel_list {
     int32_t c[SL_MAX_CHANNELS];
 };

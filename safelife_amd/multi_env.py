@@ -8,6 +8,10 @@ them may leave (safelife_game.py:537-552).  One fused launch per step (``slhip_e
 family, one workgroup per board, any board shape); an env reloads its next pool level inside the step once ALL its
 agents are done (training/base_algo.py:231-236).  Levels: the reference's ``levels/random/multi-agent`` specs, or any
 level with A agents -- ``LevelPool(levels, n_agents=A)``.
+
+With ``wrappers=``, ``side_effects=`` or ``policy_layout=`` the steps go through ``slhip_env_step_multi_ex`` /
+``_reset_multi_ex``: the reference's multi-agent training stack (training/env_factory.py:277-283) fused into the step,
+per agent (include/safelife_hip.h, sl_multi_extras).
 """
 import ctypes as C
 
@@ -23,6 +27,12 @@ class SafeLifeMultiAgentVectorEnv(object):
     pool : LevelPool(levels, n_agents=A)
     num_envs, time_limit, remove_white_goals, view_shape, output_channels, auto_reset, first_level, level_stride,
     env_offset, episode_streams, points_on_level_exit : as SafeLifeVectorEnv.
+    wrappers, side_effects, policy_layout : the keys and meaning of SafeLifeVectorEnv's, per agent:
+        ``shaped_reward``  float32 [B, A]: what the outermost wrapper returns (each wrapper rounds to float32, as the
+                           reference's in-place updates of its float32 reward array do); done agents keep being shaped
+        ``policy_tensor``  [B, A, C, view_w, view_h] uint8 / float32
+        ``side_effects_flush()``: a ``SideEffectBatch`` with one entry per env EPISODE (queued on the step where every
+                           agent is done), whose ``agent_records()`` hold every agent's record of that step
 
     ``reset()`` -> obs;  ``step(actions)`` -> (obs, reward, done, info) with
         actions  int   [B, A]   0..8 (an agent that is done takes 0: training/base_algo.py:216-219)
@@ -36,7 +46,8 @@ class SafeLifeMultiAgentVectorEnv(object):
 
     def __init__(self, pool, num_envs, *, time_limit=1000, remove_white_goals=True, view_shape=(15, 15),
                  output_channels=tuple(range(16)) + (25, 26, 27), auto_reset=True, first_level=None, level_stride=1,
-                 env_offset=0, with_obs=True, points_on_level_exit=1, episode_streams=True):
+                 env_offset=0, with_obs=True, points_on_level_exit=1, episode_streams=True, wrappers=None,
+                 side_effects=None, policy_layout=None):
         import torch
         if not isinstance(pool, LevelPool) or getattr(pool, "n_agents", 1) < 1:
             raise TypeError("pool must be a LevelPool")
@@ -48,7 +59,7 @@ class SafeLifeMultiAgentVectorEnv(object):
                                              view_shape=view_shape, output_channels=output_channels, auto_reset=auto_reset,
                                              first_level=first_level, level_stride=level_stride, env_offset=env_offset,
                                              with_obs=False, points_on_level_exit=points_on_level_exit,
-                                             episode_streams=episode_streams)
+                                             episode_streams=episode_streams, wrappers=wrappers, side_effects=side_effects)
         self.torch, self.pool, self.device = torch, pool, base.device
         self.num_envs, self.n_agents = int(num_envs), A
         B = self.num_envs
@@ -88,14 +99,62 @@ class SafeLifeMultiAgentVectorEnv(object):
         self.done = flags[:, :, 0]
         self.info = {"success": flags[:, :, 1], "times_up": flags[:, :, 2],
                      "episode_reward": out[:, :, 2].view(torch.float32), "episode_length": out[:, :, 3]}
+        self.shaped_reward = self.policy_tensor = None
+        self._x = None
+        if wrappers or side_effects or policy_layout is not None:
+            self._setup_extras(wrappers, side_effects, policy_layout)
+
+    def _setup_extras(self, wrappers, side_effects, policy_layout):
+        torch, t, base, dev = self.torch, self.t, self.base, self.device
+        B, A = self.num_envs, self.n_agents
+        H, W = self.pool.shape
+        x = self.extras = _hip.MultiExtras()
+        w = base.struct.wrap
+        if w.flags:
+            # movement_bonus * speed**power with the reference's own array expression over the agents' integer distances
+            # (env_wrappers.py:80-87: speed = dist / n elementwise), every reachable distance at once
+            cfg = dict(wrappers)
+            bonus, power = cfg.get("movement_bonus"), cfg.get("movement_bonus_power", 1e-100)
+            table = np.zeros(w.move_table_len, np.float64)
+            if bonus is not None:
+                dist = np.arange(w.move_table_len)
+                table = bonus * (dist / w.move_period) ** power
+            t["move_table"] = torch.from_numpy(np.ascontiguousarray(table, np.float64)).to(dev)
+            w.move_table = t["move_table"].data_ptr()
+            t["wrap_state"] = torch.zeros((B, A, 12), dtype=torch.int32, device=dev)      # struct sl_wrap_state
+            t["shaped_reward"] = torch.zeros((B, A), dtype=torch.float32, device=dev)
+            x.wrap_state, x.shaped_reward = t["wrap_state"].data_ptr(), t["shaped_reward"].data_ptr()
+            self.shaped_reward = t["shaped_reward"]
+            if w.flags & _hip.WRAP_SIDE_EFFECT:
+                t["baseline"] = torch.zeros((self.pool.n_slots, H, W), dtype=torch.int16, device=dev)
+                x.baseline = t["baseline"].data_ptr()
+        if side_effects:
+            # the base env's queue and flush machinery, with every agent's record of the queued step next to each entry
+            base._se["agent_records"] = A
+            base._se["queue"] = base._new_queue()
+            base.struct.finished = base._se["queue"][0]
+            x.finished_agents = base._se["queue"][1]["agents"].data_ptr()
+        if policy_layout is not None:
+            chans = self.output_channels
+            if policy_layout not in ("uint8", "float32") or not chans:
+                raise ValueError("policy_layout must be 'uint8' or 'float32' and needs output_channels")
+            vh, vw = self.view_shape
+            self.policy_tensor = torch.zeros((B, A, len(chans), vw, vh), device=dev,
+                                             dtype=torch.uint8 if policy_layout == "uint8" else torch.float32)
+            x.policy_obs = self.policy_tensor.data_ptr()
+            x.policy_dtype = 0 if policy_layout == "uint8" else 1
+        self._x = C.byref(x)
 
     def reset(self, mask=None):
         """SafeLifeEnv.reset() for every env (or those with mask[e] != 0)."""
         mk = None
         if mask is not None:
             mk = self.torch.as_tensor(np.ascontiguousarray(mask, dtype=np.uint8)).to(self.device)
-        _hip.check(self._lib.slhip_env_reset_multi(self.base._sref, self._mref, None if mk is None else mk.data_ptr(),
-                                                   _hip.current_stream_ptr()))
+        mp = None if mk is None else mk.data_ptr()
+        if self._x is not None:
+            _hip.check(self._lib.slhip_env_reset_multi_ex(self.base._sref, self._mref, self._x, mp, _hip.current_stream_ptr()))
+        else:
+            _hip.check(self._lib.slhip_env_reset_multi(self.base._sref, self._mref, mp, _hip.current_stream_ptr()))
         if mk is not None:
             self.torch.cuda.current_stream().synchronize()      # (the mask tensor is the call's own)
         return self.obs
@@ -106,8 +165,26 @@ class SafeLifeMultiAgentVectorEnv(object):
         if tuple(a.shape) != (self.num_envs, self.n_agents):
             raise ValueError("actions must have shape [num_envs, n_agents]")
         self._actions = a                                       # (alive until the next step)
-        _hip.check(self._lib.slhip_env_step_multi(self.base._sref, self._mref, a.data_ptr(), _hip.current_stream_ptr()))
+        if self._x is not None:
+            _hip.check(self._lib.slhip_env_step_multi_ex(self.base._sref, self._mref, self._x, a.data_ptr(),
+                                                         _hip.current_stream_ptr()))
+        else:
+            _hip.check(self._lib.slhip_env_step_multi(self.base._sref, self._mref, a.data_ptr(), _hip.current_stream_ptr()))
+        self.base.steps_dispatched += 1
         return self.obs, self.reward, self.done, self.info
+
+    def side_effects_flush(self, overlap=False, defer=False):
+        """The base env's ``side_effects_flush()`` over the episodes this env queued (one entry per env episode; the
+        returned batch's ``agent_records()`` has every agent's record of the step that ended it)."""
+        batch = self.base.side_effects_flush(overlap=overlap, defer=defer)
+        self.extras.finished_agents = self.base._se["queue"][1]["agents"].data_ptr()
+        return batch
+
+    def side_effects_launch(self):
+        self.base.side_effects_launch()
+
+    def side_effects_join(self):
+        self.base.side_effects_join()
 
     def numpy(self, name):
         """Host copy of a state array: the single-agent env's names for what the env owns (board, goals, rng, num_steps,
@@ -124,6 +201,11 @@ class SafeLifeMultiAgentVectorEnv(object):
             return col.view(np.float32) if name == "episode_reward" else col
         if name == "reward":
             return self.reward.cpu().numpy()
+        if name == "shaped_reward":
+            return self.shaped_reward.cpu().numpy()
+        if name in ("wrap_state", "baseline"):
+            a = self.t[name].cpu().numpy()
+            return a.view(np.uint16) if name == "baseline" else a
         if name == "done":
             return self.done.cpu().numpy()
         if name in ("success", "times_up"):

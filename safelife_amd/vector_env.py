@@ -41,11 +41,13 @@ class SideEffectBatch(object):
     ``boards``     the boards as the agents left them, uint16 payload [C,H,W]
     ``counts``     int32 [2,C,H,W,8]: the two ``life_occupancy`` tensors (inaction, action) of side_effects.py:109-110
     ``keys`` / ``life_dist`` / ``type_masks``: the distributions of :111-130 (include/safelife_hip.h)
+    ``agents``     int32 [C,A,4] (multi-agent envs): every agent's ``struct sl_step_out`` of the step that queued the entry
     """
 
     def __init__(self, env, queue_bufs, out, num_samples, done=None):
         self.env, self.num_samples = env, num_samples
         self.count, self.rec_tensor, self.boards = queue_bufs["count"], queue_bufs["records"], queue_bufs["boards"]
+        self.agents = queue_bufs.get("agents")
         self.counts, self.keys = out["counts"], out["keys"]
         self.life_dist, self.type_masks = out["life_dist"], out["type_masks"]
         self._keep = out
@@ -76,6 +78,17 @@ class SideEffectBatch(object):
         return dict(env=raw[:, 0], level=raw[:, 1], num_steps=raw[:, 2], episode_idx=raw[:, 3],
                     spawn_prob=raw[:, 4].copy().view(np.float32), episode_reward=raw[:, 5].copy().view(np.float32),
                     episode_length=raw[:, 6], success=flags[:, 0], times_up=flags[:, 1], n_cell_types=flags[:, 2])
+
+    def agent_records(self):
+        """Multi-agent envs: host view of every agent's record of the valid entries' last step, arrays [n, A] (reward,
+        done, success, times_up, episode_reward, episode_length)."""
+        if self.agents is None:
+            raise ValueError("agent_records() belongs to the batches of a multi-agent env")
+        n = len(self)
+        raw = self.agents[:n].cpu().numpy()
+        flags = raw[:, :, 1:2].copy().view(np.uint8)
+        return dict(reward=raw[:, :, 0].copy().view(np.float32), done=flags[:, :, 0], success=flags[:, :, 1],
+                    times_up=flags[:, :, 2], episode_reward=raw[:, :, 2].copy().view(np.float32), episode_length=raw[:, :, 3])
 
     def dropped(self):
         """Episodes that ended while the queue was full (they were not recorded)."""
@@ -1069,6 +1082,8 @@ class SafeLifeVectorEnv(object):
         bufs = dict(count=torch.zeros(1, dtype=torch.int32, device=self.device),
                     records=torch.zeros((cap, 8), dtype=torch.int32, device=self.device),
                     boards=torch.zeros((cap, H, W), dtype=torch.int16, device=self.device))
+        if self._se.get("agent_records"):           # (a multi-agent env's: every agent's record of the queued step)
+            bufs["agents"] = torch.zeros((cap, self._se["agent_records"], 4), dtype=torch.int32, device=self.device)
         q = _hip.EpisodeQueue()
         q.capacity, q.env_base = cap, 0
         q.count, q.records, q.boards = (bufs[k].data_ptr() for k in ("count", "records", "boards"))
