@@ -460,8 +460,7 @@ int slhip_queues_selftest(void *handle, int what, int arg);
  * use_rng), so there is nothing to be stream-compatible with; every entry gets its own PCG64 stream derived
  * from its level's generator, env index and episode index, consumed in the reference's order (roll-forward,
  * inaction tensor, action tensor); derive_streams == 0 takes the caller's work_rng [C] as they are instead (how
- * the reference's recorded generator states are replayed).  The earth-mover distances stay on the host (pyemd:
- * parity unpinned).
+ * the reference's recorded generator states are replayed).  The earth-mover distances: slhip_emd_batch below.
  * All buffers are caller-owned device memory sized by the queue's capacity C:
  *   work_boards  uint16 [2C,H,W]     run 0: b0 (rolled forward in place when derive_streams == 0); run 1: copies of
  *                                    the final boards (derive_streams != 0: both runs are worked on by ONE fused
@@ -478,6 +477,34 @@ int slhip_queues_selftest(void *handle, int what, int arg);
 int slhip_side_effects(const sl_env_batch *env, const sl_episode_queue *queue, int num_samples, int derive_streams,
                        uint16_t *work_boards, float *work_prob, int32_t *work_steps, sl_pcg64 *work_rng,
                        int32_t *counts, uint16_t *keys, double *life_dist, uint8_t *type_masks, void *stream);
+
+/* The earth-mover distances of side_effect_score() (side_effects.py:13-57,132-154) for every entry of `queue` and
+ * every key slot, from the outputs of slhip_side_effects (counts, keys, type_masks; the record's n_cell_types), on
+ * the device and without a host read; stops at min(*queue->count, capacity) like the other stages.  Per (entry, key):
+ * a, b = the inaction / action distribution; the cells with |a - b| > 1e-3 * max|a - b| take part; the result is the
+ * EMD-hat of Pele & Werman over them -- the minimum-cost flow of min(sum a, sum b) under the ground distance, plus
+ * extra_mass_penalty * |sum a - sum b| -- solved EXACTLY (successive shortest paths on integer flows; only the final
+ * sum(flow * cost) is floating point, in a fixed order: the result is deterministic).  Any H, W <= 64.
+ *   ground       double [(2H-1),(2W-1)]: ground[dr + H-1][dc + W-1] = distance from a cell to the cell dr rows and
+ *                dc columns before it (row_i - row_j, col_i - col_j: the reference's rule is asymmetric); built by the
+ *                host (safelife_amd.side_effects.ground_table) so that both sides price arcs with the same bits.
+ *                Must be a quasi-metric: 0 at (0,0) and obeying the triangle inequality (sl_emd.hip says why).
+ *   extra_mass_penalty  >= 0 (the reference's default: 1.0)
+ *   workspace    device memory, 256-byte aligned, slhip_emd_workspace_bytes(H, W, capacity, concurrency) bytes:
+ *                256 + concurrency * (align256(2 * M * M) + align256(36 * (H*W + 2))), M = H*W/2 + 1
+ *                (`concurrency` workgroups each solve one problem at a time and take the next off a device counter)
+ *   scores       double [C,SL_SE_MAX_KEYS,2] out: distance, inaction mass (sum a over the board); NaN, NaN for an
+ *                empty key slot, and for every slot of an entry whose keys were cut short (n_cell_types >
+ *                SL_SE_MAX_KEYS - 8: evaluate those on the host).  Entries past the count are not written.
+ *   n_cells      int32 [C,SL_SE_MAX_KEYS] out: participating cells (0 for an empty slot, -1 for a cut-short entry)
+ * Every loop of the solver is bounded by the problem's size; a problem that runs over a bound gets NaN scores and
+ * slhip_emd_status(workspace, stream) -- which synchronises the stream -- returns SL_E_HIP naming it. */
+size_t slhip_emd_workspace_bytes(int H, int W, int capacity, int concurrency);
+int slhip_emd_batch(const sl_episode_queue *queue, int H, int W, int num_samples, const int32_t *counts,
+                    const uint16_t *keys, const uint8_t *type_masks, const double *ground, double extra_mass_penalty,
+                    void *workspace, size_t workspace_bytes, int concurrency, double *scores, int32_t *n_cells,
+                    void *stream);
+int slhip_emd_status(const void *workspace, void *stream);
 
 /* ---- multi-GPU: the per-step records of every rank's envs -> rank 0 ----------------------------
  * Boards never cross GPUs; the only exchange of the path is what a learner on rank 0 needs from the other ranks:

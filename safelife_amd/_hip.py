@@ -24,6 +24,7 @@ EXPORTS = (
     "slhip_streams_concurrent", "slhip_streams_order",
     "slhip_env_obs", "slhip_env_step_multi", "slhip_env_reset_multi", "slhip_env_step_multi_ex", "slhip_env_reset_multi_ex",
     "slhip_obs_to_policy", "slhip_sample_actions", "slhip_side_effects",
+    "slhip_emd_workspace_bytes", "slhip_emd_batch", "slhip_emd_status",
     "slhip_gather_unique_id", "slhip_gather_init", "slhip_gather_window", "slhip_gather_destroy",
     "slhip_gather_window_async", "slhip_gather_done", "slhip_gather_wait_streams",
     "slhip_gather_window_queued",
@@ -214,6 +215,12 @@ def lib():
             L.slhip_queues_selftest.argtypes = [C.c_void_p, C.c_int, C.c_int]
             L.slhip_gather_window_queued.argtypes = [_p, _p, _p, C.c_size_t, C.c_void_p, _p, C.POINTER(C.c_longlong)]
         L.slhip_side_effects.argtypes = [C.POINTER(EnvBatch), C.POINTER(EpisodeQueue), C.c_int, C.c_int] + [_p] * 9
+        if hasattr(L, "slhip_emd_batch"):
+            L.slhip_emd_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+            L.slhip_emd_workspace_bytes.restype = C.c_size_t
+            L.slhip_emd_batch.argtypes = [C.POINTER(EpisodeQueue), C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, C.c_double,
+                                          _p, C.c_size_t, C.c_int, _p, _p, _p]
+            L.slhip_emd_status.argtypes = [_p, _p]
         if hasattr(L, "slhip_sample_actions"):
             L.slhip_sample_actions.argtypes = [_p, C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, _p, _p]
         L.slhip_obs_to_policy.argtypes = [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]

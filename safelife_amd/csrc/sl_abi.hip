@@ -1443,6 +1443,44 @@ int slhip_side_effects(const sl_env_batch *env, const sl_episode_queue *queue, i
     return err == hipSuccess ? SL_OK : hip_fail(err, "side_effects launch");
 }
 
+size_t slhip_emd_workspace_bytes(int H, int W, int capacity, int concurrency) {
+    if (H < 1 || W < 1 || H > 64 || W > 64 || capacity < 0 || concurrency < 1) return 0;
+    return sl::emd_workspace_bytes(H, W, concurrency);
+}
+
+int slhip_emd_batch(const sl_episode_queue *queue, int H, int W, int num_samples, const int32_t *counts,
+                    const uint16_t *keys, const uint8_t *type_masks, const double *ground, double extra_mass_penalty,
+                    void *workspace, size_t workspace_bytes, int concurrency, double *scores, int32_t *n_cells,
+                    void *stream) {
+    if (!queue || queue->capacity < 0) return fail(SL_E_ARG, "bad queue");
+    if (H < 1 || W < 1 || H > 64 || W > 64) return fail(SL_E_SHAPE, "emd: board shape outside 1..64 x 1..64");
+    if (num_samples < 1 || num_samples > 65535) return fail(SL_E_ARG, "num_samples outside 1..65535");
+    if (!(extra_mass_penalty >= 0.0))
+        return fail(SL_E_UNSUPPORTED, "emd: extra_mass_penalty < 0 (the largest ground distance) is a host-path option");
+    if (concurrency < 1 || concurrency > 65535) return fail(SL_E_ARG, "emd: concurrency outside 1..65535");
+    if (queue->capacity == 0) return SL_OK;
+    if ((size_t)queue->capacity * SL_SE_MAX_KEYS > (size_t)INT32_MAX) return fail(SL_E_ARG, "emd: capacity too large");
+    if (!queue->count || !queue->records || !counts || !keys || !type_masks || !ground || !workspace || !scores || !n_cells)
+        return fail(SL_E_ARG, "null pointer");
+    if (((uintptr_t)workspace & 255) || workspace_bytes < sl::emd_workspace_bytes(H, W, concurrency))
+        return fail(SL_E_ARG, "emd: workspace unaligned (256 bytes) or smaller than slhip_emd_workspace_bytes()");
+    const hipError_t err = sl::launch_emd(*queue, H, W, num_samples, counts, keys, type_masks, ground, extra_mass_penalty,
+                                          workspace, concurrency, scores, n_cells, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "emd launch");
+}
+
+int slhip_emd_status(const void *workspace, void *stream) {
+    if (!workspace) return fail(SL_E_ARG, "null pointer");
+    int header[2] = {0, 0};
+    hipError_t err = hipMemcpyAsync(header, workspace, sizeof(header), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (err == hipSuccess) err = hipStreamSynchronize((hipStream_t)stream);
+    if (err != hipSuccess) return hip_fail(err, "emd status");
+    if (header[1])
+        return fail(SL_E_HIP, "emd: problem " + std::to_string(header[1] - 1) + " ran over a loop bound of the solver (its "
+                              "scores are NaN)");
+    return SL_OK;
+}
+
 static int check_multi(const sl_env_batch *env, const sl_multi_agent *m) {
     int rc = check_env(env);
     if (rc) return rc;

@@ -68,6 +68,11 @@ hipError_t launch_se_gather(const sl_env_batch &env, const sl_episode_queue &q, 
 hipError_t launch_se_distributions(const sl_env_batch &env, const sl_episode_queue &q, const int32_t *counts,
                                    double denominator, uint16_t *keys, double *life_dist, uint8_t *type_masks,
                                    hipStream_t stream);
+// sl_emd.hip : the earth-mover distances of every (entry, key) of the pass's outputs (workspace rule: see the file)
+size_t emd_workspace_bytes(int H, int W, int concurrency);
+hipError_t launch_emd(const sl_episode_queue &q, int H, int W, int num_samples, const int32_t *counts,
+                      const uint16_t *keys, const uint8_t *type_masks, const double *ground, double penalty,
+                      void *workspace, int concurrency, double *scores, int32_t *n_cells, hipStream_t stream);
 // envs [e_first, e_first + e_count) of the batch; actions / reward_t / done_t are indexed [t * tstride + e]
 // with the env's index in the whole batch
 // (sl_aql.hip dispatches the same kernel from queues of the library's own: PreparedStep below)

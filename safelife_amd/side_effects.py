@@ -6,12 +6,15 @@ reference (tests/golden/side_effect_inputs.npz): the roll-forward of the untouch
 (``advance_board(b0, p, num_steps)``, side_effects.py:108), the two ``life_occupancy`` tensors
 (:109-110) and the per-cell-type distributions built from them (:111-130).
 
-The distance itself is NOT pinned.  The reference calls ``pyemd.emd`` (pyemd==0.5.1, not vendored, not
-installed here, no reference test fixes its output).  ``earth_mover_distance`` below restates the
-published definition pyemd implements -- Pele & Werman's EMD-hat: the minimum-cost flow that moves
-``min(sum a, sum b)`` mass, plus ``extra_mass_penalty * |sum a - sum b|`` -- and solves the
-transportation LP with scipy's HiGHS.  Expect agreement with pyemd to solver tolerance (~1e-9), not
-to the bit.
+The distance runs on the GPU too: ``SideEffectBatch.scores_all()`` / ``scores(i, device=True)`` solve every
+(entry, cell type) transport problem of a batch exactly in one launch (``slhip_emd_batch``, csrc/sl_emd.hip),
+pinned against ``earth_mover_distance`` below (tests/test_emd.py, tests/golden/emd_cases.npz).  What is NOT pinned
+is parity with pyemd itself: the reference calls ``pyemd.emd`` (pyemd==0.5.1, not vendored, not installed here, no
+reference test fixes its output).  ``earth_mover_distance`` restates the published definition pyemd implements --
+Pele & Werman's EMD-hat: the minimum-cost flow that moves ``min(sum a, sum b)`` mass, plus
+``extra_mass_penalty * |sum a - sum b|`` -- and solves the transportation LP with scipy's HiGHS; host and device
+share the ground-distance table (``ground_table``).  Expect agreement with pyemd to solver tolerance (~1e-9), not to
+the bit.
 """
 import numpy as np
 
@@ -87,7 +90,7 @@ def distributions_from_counts(b0, b2, counts, denominator):
     return inaction, action
 
 
-def _emd_hat(a, b, dist, extra_mass_penalty):
+def _emd_hat(a, b, dist, extra_mass_penalty, method="highs", options=None):
     """min-cost flow of min(sum a, sum b) from a to b + penalty * |sum a - sum b| (Pele & Werman 2009)."""
     from scipy.optimize import linprog
     from scipy.sparse import identity, kron, csr_matrix
@@ -102,7 +105,7 @@ def _emd_hat(a, b, dist, extra_mass_penalty):
         col_sum = kron(ones, identity(n, format="csr"), format="csr")      # sum_i f_ij <= b_j
         total = csr_matrix(np.ones((1, n * n)))                            # sum f = moved
         res = linprog(dist.reshape(-1), A_ub=_vstack(row_sum, col_sum), b_ub=np.concatenate([a, b]),
-                      A_eq=total, b_eq=[moved], bounds=(0, None), method="highs")
+                      A_eq=total, b_eq=[moved], bounds=(0, None), method=method, options=options)
         if res.status != 0:
             raise RuntimeError("transportation LP failed: %s" % res.message)
         cost = float(res.fun)
@@ -116,21 +119,37 @@ def _vstack(a, b):
     return vstack([a, b], format="csr")
 
 
-def _axis_gap(coord, size, wrap):
-    """Pairwise ground distance along one axis between the cells at `coord` (int vector): the signed difference
-    c_i - c_j, and with `wrap` the smaller of it and size - (c_i - c_j).  That is the reference's torus rule
-    exactly as it stands (side_effects.py:47-50): the minimum is taken on the SIGNED difference, so only pairs with
-    c_i > c_j can take the short way round -- the matrix is not symmetric, and parity with pyemd's input needs it so."""
-    gap = coord[:, None] - coord[None, :]
+def _signed_gap(gap, size, wrap):
+    """The reference's torus rule on an array of SIGNED coordinate differences c_i - c_j (side_effects.py:47-50): with
+    `wrap` the smaller of the difference and size - difference.  The minimum is taken on the signed value, so only
+    pairs with c_i > c_j can take the short way round -- not symmetric, and parity with pyemd's input needs it so."""
     return np.minimum(gap, size - gap) if wrap else gap
 
 
-def _ground_distance(rows, cols, shape, metric, wrap_x, wrap_y, tanh_scale):
-    """Distance matrix between the cells (rows[k], cols[k]) of a board of `shape` (side_effects.py:38-56)."""
-    gy = _axis_gap(rows, shape[0], wrap_y)
-    gx = _axis_gap(cols, shape[1], wrap_x)
+def _axis_gap(coord, size, wrap):
+    """Pairwise ground distance along one axis between the cells at `coord` (int vector): `_signed_gap` of
+    c_i - c_j."""
+    return _signed_gap(coord[:, None] - coord[None, :], size, wrap)
+
+
+def ground_table(shape, metric="manhattan", wrap_x=True, wrap_y=True, tanh_scale=5.0):
+    """Ground distance by signed offset, float64 ``[2H-1, 2W-1]``: ``table[dr + H-1, dc + W-1]`` is the distance from a
+    cell to the cell ``dr`` rows and ``dc`` columns before it (``dr = row_i - row_j``).  The distance depends on nothing
+    else, so this is all of it; the host LP's matrix is read out of this table (`_ground_distance`) and the device
+    solver (``slhip_emd_batch``) is given the same table: both price every arc with the same bits."""
+    H, W = int(shape[0]), int(shape[1])
+    gy = _signed_gap(np.arange(-(H - 1), H), H, wrap_y)[:, None]
+    gx = _signed_gap(np.arange(-(W - 1), W), W, wrap_x)[None, :]
     dist = np.hypot(gx, gy) if metric != "manhattan" else np.abs(gx).astype(float) + np.abs(gy)
-    return np.tanh(dist / tanh_scale) if tanh_scale > 0 else dist
+    return np.ascontiguousarray(np.tanh(dist / tanh_scale) if tanh_scale > 0 else dist, dtype=np.float64)
+
+
+def _ground_distance(rows, cols, shape, metric, wrap_x, wrap_y, tanh_scale):
+    """Distance matrix between the cells (rows[k], cols[k]) of a board of `shape` (side_effects.py:38-56), read out of
+    `ground_table`."""
+    table = ground_table(shape, metric, wrap_x, wrap_y, tanh_scale)
+    rows, cols = np.asarray(rows), np.asarray(cols)
+    return table[rows[:, None] - rows[None, :] + shape[0] - 1, cols[:, None] - cols[None, :] + shape[1] - 1]
 
 
 def earth_mover_distance(a, b, metric="manhattan", wrap_x=True, wrap_y=True, tanh_scale=5.0,
@@ -167,12 +186,17 @@ def _as_u16(board):
     return a.view(np.uint16) if a.dtype == np.int16 else a.astype(np.uint16, copy=False)
 
 
-def _scores(inaction, action, shape, include, exclude, strkeys):
-    keys = set(inaction)
+def _select_keys(keys, include, exclude, strkeys):
+    keys = set(keys)
     if include is not None:
         keys &= set(name_to_cell(k) for k in include) if strkeys else set(include)
     if exclude is not None:
         keys -= set(name_to_cell(k) for k in exclude) if strkeys else set(exclude)
+    return keys
+
+
+def _scores(inaction, action, shape, include, exclude, strkeys):
+    keys = _select_keys(inaction, include, exclude, strkeys)
     zeros = np.zeros(shape)
     scores = {k: [earth_mover_distance(inaction.get(k, zeros), action.get(k, zeros)),
                   np.sum(inaction.get(k, zeros))] for k in keys}

@@ -24,6 +24,9 @@ from .levels import LevelPool, PreparedLevels
 _DEFAULT_CHANNELS = tuple(range(16)) + (25, 26, 27)      # safelife_env.py:71
 
 
+_EMD_TABLES = {}        # (device, H, W) -> the ground-distance table of side_effects.ground_table, uploaded once
+
+
 class _EventSet(object):
     def __init__(self, events):
         self.events = list(events)
@@ -41,6 +44,7 @@ class SideEffectBatch(object):
     ``boards``     the boards as the agents left them, uint16 payload [C,H,W]
     ``counts``     int32 [2,C,H,W,8]: the two ``life_occupancy`` tensors (inaction, action) of side_effects.py:109-110
     ``keys`` / ``life_dist`` / ``type_masks``: the distributions of :111-130 (include/safelife_hip.h)
+    ``scores_all()``: the earth-mover distances of every entry and key, solved on the device
     ``agents``     int32 [C,A,4] (multi-agent envs): every agent's ``struct sl_step_out`` of the step that queued the entry
     """
 
@@ -52,6 +56,7 @@ class SideEffectBatch(object):
         self.life_dist, self.type_masks = out["life_dist"], out["type_masks"]
         self._keep = out
         self._done = done       # event behind the pass when it ran on the env's side stream (overlap=True)
+        self._emd = None        # scores_all()'s tensors, once computed
         # (the host fallback of distributions() reads an entry's starting board from the host pool by physical slot: which
         #  rewrite of every slot this batch belongs to)
         ver = getattr(env.pool, "slot_version", None)
@@ -125,12 +130,92 @@ class SideEffectBatch(object):
                 inaction[int(key)], action[int(key)] = 1.0 * masks[0, k - 8], 1.0 * masks[1, k - 8]
         return inaction, action
 
-    def scores(self, i, include=None, exclude=None, strkeys=True, weights=None):
-        """``side_effect_score`` of entry i (earth-mover distances on the host; safelife_env.py:185-192 for
-        ``weights``)."""
+    def scores_all(self, weights=None, concurrency=None):
+        """The earth-mover distances of EVERY entry and key, on the device (``slhip_emd_batch``: one launch, exact
+        solver, csrc/sl_emd.hip) -- launched behind the pass on the stream the pass ran on, nothing read back.  Computed
+        once per batch.  Returns device tensors: ``scores`` float64 [C,K,2] (distance, inaction mass per key slot; NaN
+        for an empty slot, for entries past the count, and for entries whose keys were cut short -- ``n_cells`` is -1
+        there and ``scores(i, device=True)`` evaluates them on the host), ``keys`` [C,K], ``n_cells`` int32 [C,K] (cells
+        that took part), and with ``weights`` (``{cell name: weight}``, safelife_env.py:185-192) ``total`` [C,2].
+        ``concurrency``: workgroups solving at once, each with a workspace slice of its own (default: up to 256,
+        fewer where that would take more than 1 GiB -- 8.5 MB per workgroup at 64x64)."""
         from . import side_effects as se
-        inaction, action = self.distributions(i)
-        out = se._scores(inaction, action, tuple(self.boards.shape[1:]), include, exclude, strkeys)
+        torch, lib = self.env.torch, _hip.lib()
+        side = None
+        if self._done is not None:
+            self.env.side_effects_launch()          # (a deferred pass nobody has launched yet)
+            side = self.env._se["stream"]
+        if self._emd is None:
+            cap, K = self.rec_tensor.shape[0], _hip.SL_SE_MAX_KEYS
+            H, W = int(self.boards.shape[1]), int(self.boards.shape[2])
+            dev = self.counts.device
+            per_slot = lib.slhip_emd_workspace_bytes(H, W, cap, 2) - lib.slhip_emd_workspace_bytes(H, W, cap, 1)
+            conc = int(concurrency or max(1, min(256, cap * K, (1 << 30) // per_slot)))
+            size = lib.slhip_emd_workspace_bytes(H, W, cap, conc)
+            table = _EMD_TABLES.get((dev, H, W))
+            if table is None:
+                table = _EMD_TABLES[(dev, H, W)] = torch.from_numpy(se.ground_table((H, W))).to(dev)
+            ws = self._keep.get("emd_workspace")
+            if ws is None or ws.numel() < size:
+                ws = self._keep["emd_workspace"] = torch.empty(size, dtype=torch.uint8, device=dev)
+            emd = dict(scores=torch.full((cap, K, 2), float("nan"), dtype=torch.float64, device=dev),
+                       n_cells=torch.zeros((cap, K), dtype=torch.int32, device=dev), workspace=ws, table=table,
+                       checked=False)
+            q = _hip.EpisodeQueue()
+            q.capacity, q.env_base = cap, 0
+            q.count, q.records, q.boards = self.count.data_ptr(), self.rec_tensor.data_ptr(), self.boards.data_ptr()
+            if side is not None:                      # (the tensors above were made on the caller's stream)
+                side.wait_stream(torch.cuda.current_stream())
+                for tns in (emd["scores"], emd["n_cells"], ws, table):
+                    tns.record_stream(side)
+            stream_ptr = _hip.current_stream_ptr() if side is None else C.c_void_p(side.cuda_stream)
+            _hip.check(lib.slhip_emd_batch(C.byref(q), H, W, self.num_samples, _hip.ptr(self.counts), _hip.ptr(self.keys),
+                                           _hip.ptr(self.type_masks), _hip.ptr(table), 1.0, _hip.ptr(ws), size, conc,
+                                           _hip.ptr(emd["scores"]), _hip.ptr(emd["n_cells"]), stream_ptr))
+            if side is not None:
+                self._done.record(side)               # wait() / side_effects_join() now order against the distances too
+            self._emd = emd
+        out = dict(scores=self._emd["scores"], keys=self.keys, n_cells=self._emd["n_cells"])
+        if weights is not None:
+            lut = np.zeros(65536)
+            for name, weight in weights.items():
+                lut[se.name_to_cell(name)] += weight
+            lut[0xFFFF] = 0.0                         # (an empty key slot)
+            with torch.cuda.stream(side if side is not None else torch.cuda.current_stream()):
+                per_key = torch.from_numpy(lut).to(self.keys.device)[self.keys.to(torch.int64) & 0xFFFF]
+                total = (torch.nan_to_num(out["scores"]) * per_key[:, :, None]).sum(1)
+                total[out["n_cells"][:, 0] < 0] = float("nan")
+                if side is not None:
+                    total.record_stream(side)
+                    self._done.record(side)
+            out["total"] = total
+        return out
+
+    def scores(self, i, include=None, exclude=None, strkeys=True, weights=None, device=False):
+        """``side_effect_score`` of entry i (safelife_env.py:185-192 for ``weights``).  ``device=False``: the
+        earth-mover distances are solved on the host, one LP per cell type.  ``device=True``: they are read from
+        ``scores_all()`` (the whole batch in one launch, cached); an entry whose keys were cut short on the device
+        still takes the host path."""
+        from . import side_effects as se
+        out = None
+        if device:
+            emd = self.scores_all()
+            self.wait()
+            if not self._emd["checked"]:
+                _hip.check(_hip.lib().slhip_emd_status(_hip.ptr(self._emd["workspace"]), _hip.current_stream_ptr()))
+                self._emd["checked"] = True
+            if not 0 <= i < len(self):
+                raise IndexError("entry %d of a batch of %d" % (i, len(self)))
+            if int(emd["n_cells"][i, 0].item()) >= 0:
+                keys = self.keys[i].cpu().numpy().view(np.uint16)
+                vals = emd["scores"][i].cpu().numpy()
+                found = {int(key): vals[k].tolist() for k, key in enumerate(keys) if key != 0xFFFF}
+                out = {k: found[k] for k in se._select_keys(found, include, exclude, strkeys)}
+                if strkeys:
+                    out = {se.cell_name(k): v for k, v in out.items()}
+        if out is None:
+            inaction, action = self.distributions(i)
+            out = se._scores(inaction, action, tuple(self.boards.shape[1:]), include, exclude, strkeys)
         if weights is not None:
             total = np.zeros(2)
             for key, weight in weights.items():
