@@ -92,56 +92,16 @@ def _closed_forms():
 # ---------------------------------------------------------------------------------------------------- GPU
 
 def _run_cases(group, shape, den, concurrency=None, repeat=1):
-    """slhip_emd_batch on a queue with one entry per case: occupancy-count cases (den > 1) sit in life-colour slot
-    (index % 8), mask cases (den == 1) in cell-type slot 8 + index % 16.  Returns (scores [n,2], n_cells [n]) per run."""
-    import torch
+    """slhip_emd_batch on a queue with one entry per case (tests/emd_queue.py packs and runs it, and checks the
+    sentinels: entries past the count untouched, NaN / 0 in empty key slots): occupancy-count cases (den > 1) sit in
+    life-colour slot (index % 8), mask cases (den == 1) in cell-type slot 8 + index % 16.  Returns (scores [n,2],
+    n_cells [n]) per run."""
     from safelife_amd import _hip
-    lib, dev = _hip.lib(), _hip.device()
-    H, W = shape
-    n, K = len(group), _hip.SL_SE_MAX_KEYS
-    cap = n + 3
-    counts = np.zeros((2, cap, H, W, 8), np.int32)
-    masks = np.zeros((cap, 2, K - 8, H, W), np.uint8)
-    keys = np.full((cap, K), 0xFFFF, np.uint16)
-    slots = []
-    for i, c in enumerate(group):
-        if den > 1:
-            k = i % 8
-            counts[0, i, :, :, k], counts[1, i, :, :, k] = c["a"], c["b"]
-        else:
-            k = 8 + i % (K - 8)
-            masks[i, 0, k - 8], masks[i, 1, k - 8] = c["a"], c["b"]
-        keys[i, k] = 0x0100 + k
-        slots.append(k)
-    t = dict(count=torch.tensor([n], dtype=torch.int32, device=dev),
-             records=torch.zeros((cap, 8), dtype=torch.int32, device=dev),
-             counts=torch.from_numpy(counts).to(dev), keys=torch.from_numpy(keys.view(np.int16)).to(dev),
-             masks=torch.from_numpy(masks).to(dev))
-    from safelife_amd.side_effects import ground_table
-    table = torch.from_numpy(ground_table(shape)).to(dev)
-    conc = concurrency or min(64, cap * K)
-    size = lib.slhip_emd_workspace_bytes(H, W, cap, conc)
-    assert size > 0
-    ws = torch.empty(size, dtype=torch.uint8, device=dev)
-    q = _hip.EpisodeQueue()
-    q.capacity, q.env_base = cap, 0
-    q.count, q.records, q.boards = t["count"].data_ptr(), t["records"].data_ptr(), None
-    runs = []
-    for _ in range(repeat):
-        scores = torch.full((cap, K, 2), -7.0, dtype=torch.float64, device=dev)
-        n_cells = torch.full((cap, K), -7, dtype=torch.int32, device=dev)
-        _hip.check(lib.slhip_emd_batch(C.byref(q), H, W, den, _hip.ptr(t["counts"]), _hip.ptr(t["keys"]),
-                                       _hip.ptr(t["masks"]), _hip.ptr(table), 1.0, _hip.ptr(ws), size, conc,
-                                       _hip.ptr(scores), _hip.ptr(n_cells), _hip.current_stream_ptr()))
-        _hip.check(lib.slhip_emd_status(_hip.ptr(ws), _hip.current_stream_ptr()))
-        s, m = scores.cpu().numpy(), n_cells.cpu().numpy()
-        assert (s[n:] == -7.0).all() and (m[n:] == -7).all()                 # entries past the count: untouched
-        for i, k in enumerate(slots):
-            empty = np.ones(K, bool)
-            empty[k] = False
-            assert np.isnan(s[i, empty]).all() and (m[i, empty] == 0).all()   # empty key slots
-        runs.append((np.stack([s[i, k] for i, k in enumerate(slots)]), np.array([m[i, k] for i, k in enumerate(slots)])))
-    return runs
+    from tests.emd_queue import run_queue
+    K = _hip.SL_SE_MAX_KEYS
+    assert all(c["den"] == den for c in group)
+    placement = [(i, i % 8 if den > 1 else 8 + i % (K - 8)) for i in range(len(group))]
+    return run_queue(group, shape, den, concurrency=concurrency, repeat=repeat, placement=placement)
 
 
 def _groups(cases):
