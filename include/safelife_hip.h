@@ -657,6 +657,46 @@ int slhip_obs_to_policy(const uint32_t *view, int B, int vh, int vw, const int32
 int slhip_sample_actions(const float *probs, int B, int n_actions, unsigned long long seed, unsigned long long counter,
                          int32_t *actions, void *stream);
 
+/* ---- rendering: boards -> RGB frames (additive to ABI 13: two new symbols and one new struct, nothing existing changes,
+ * so SL_ABI_VERSION stays where it is) ---------------------------------------------------------------------------------
+ * The reference's render_board (fast_render.c:33-133; Python speedups._render_board, module.c:438-512) and the view of
+ * render_graphics.render_game (helper_utils.py:42-75), for N frames in one launch, bit exact with the reference: per
+ * output byte (uint8)(255.f * (bg * (1.f - mask) + mask * sprite * fg)) in fp32, left to right, nothing fused, truncated;
+ * the tile comes from the cell's type (colour and orientation bits masked off; 13 named types, empty, the agent's four
+ * orientations, anything else -- an empty cell that carries a colour included -- the "unknown" tile), fg from the cell's
+ * colour bits, bg from the GOAL's.  The edit cursor of render_graphics.render_board is not drawn.
+ *   frame n shows source frame f = index ? index[n] : n (f outside [0, n_source): an empty frame):
+ *     board + f * board_stride, goals + f * goal_stride (strides in cells; goal_stride 0: one goal array for all frames)
+ *   sprites      float32 [70,70,4], 16-byte aligned: the sheet, RGBA / 255
+ *   orientation  optional int32 [N]: replaces bits 12-13 of every cell of frame n (values 0..3)
+ *   view_h, view_w  both 0: the whole board, [N, H*14, W*14, 3].  Both > 0: a view_h x view_w window centred on
+ *     centers[s * center_stride + 0..1] (row, col; a negative row: no agent, the centre is (0,0)), toroidal -- a view
+ *     larger than the board tiles it; every entry >= 0 of exits[s * E + 0..E) (flat cell indices) has its BOARD value
+ *     painted at its position relative to the centre, clipped to the view's perimeter, later entries over earlier ones;
+ *     goals are not repainted.  s = n, or f where aux_by_index != 0 (centres and exits live with the source frames).
+ *     exits may be NULL (E is then ignored).
+ *   out          uint8 [N, vh*14, vw*14, 3] contiguous, 4-byte aligned (16-byte aligned: wide stores) */
+typedef struct sl_render_args {
+    int32_t N, H, W, n_source;
+    int32_t view_h, view_w, E, aux_by_index;
+    long long board_stride, goal_stride, center_stride;
+    const uint16_t *board, *goals;
+    const int32_t *index;
+    const float *sprites;
+    const int32_t *orientation;
+    const int32_t *centers;
+    const int32_t *exits;
+    uint8_t *out;
+} sl_render_args;
+int slhip_render_boards(const sl_render_args *args, void *stream);
+/* The current state of the envs env_ids[0..n) (device int32; NULL: envs 0..n-1, n = env->B for all of them), the view
+ * centred on the env's agent (sl_env_scalars.agent_row / agent_col) with the env's exit_locs; view 0 x 0: whole boards.
+ * Of *env only B, H, W, E, board, goals, exit_locs and scalars are read.  A multi-agent batch keeps its agents'
+ * locations in sl_agent_state: its caller passes agent 0's (row, col) through slhip_render_boards' centers with
+ * center_stride = n_agents * 12 (render_game centres on agent_locs[0]). */
+int slhip_env_render(const sl_env_batch *env, const int32_t *env_ids, int n, int view_h, int view_w,
+                     const float *sprites, uint8_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@ cellular-automaton step of ``safelife/speedups_src`` and the integer glue of
 * ``vector_env``  ``SafeLifeVectorEnv``: B device-resident envs, one fused launch per step
 * ``game`` / ``env``  ``SafeLifeGame`` / ``SafeLifeEnv`` look-alikes (one env at a time) built on
   ``speedups`` so reference-style wrappers and training loops run unchanged
+* ``render``      boards -> RGB frames (``render_board`` / ``render_game`` look-alikes) on the device
 * ``levels``      ``.npz`` level loader and the device level pool
 * ``sharding``    one process per GPU: env partition + reward/done gather over RCCL
 * ``csrc/``       hand-written HIP kernels and the C-ABI (include/safelife_hip.h)
@@ -36,4 +37,4 @@ from .cell_types import CellTypes, DEFAULT_POINTS_TABLE  # noqa: F401,E402
 __version__ = "0.1.0"
 
 __all__ = ["CellTypes", "DEFAULT_POINTS_TABLE", "speedups", "levels", "vector_env", "game", "env",
-           "sharding"]
+           "sharding", "render"]

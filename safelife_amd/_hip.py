@@ -30,6 +30,7 @@ EXPORTS = (
     "slhip_gather_window_queued",
     "slhip_queues_open", "slhip_queues_open_on", "slhip_queues_stream_shares", "slhip_gather_stream_shares", "slhip_gather_poke", "slhip_queues_mode", "slhip_queues_steps", "slhip_queues_step", "slhip_queues_stage", "slhip_queues_go", "slhip_queues_marker",
     "slhip_queues_wait", "slhip_queues_sync", "slhip_queues_close", "slhip_queues_selftest",
+    "slhip_render_boards", "slhip_env_render",
 )
 QUEUES_RELEASE_FREE = 1
 QUEUES_STAGE_MAX = 48
@@ -133,6 +134,13 @@ class MultiExtras(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class RenderArgs(C.Structure):
+    """struct sl_render_args"""
+    _fields_ = ([(n, C.c_int32) for n in ("N", "H", "W", "n_source", "view_h", "view_w", "E", "aux_by_index")]
+                + [(n, C.c_longlong) for n in ("board_stride", "goal_stride", "center_stride")]
+                + [(n, C.c_void_p) for n in ("board", "goals", "index", "sprites", "orientation", "centers", "exits", "out")])
+
+
 class EnvBatch(C.Structure):
     _fields_ = (
         [(n, C.c_int32) for n in ENV_SCALARS_HEAD]
@@ -223,6 +231,8 @@ def lib():
             L.slhip_emd_status.argtypes = [_p, _p]
         if hasattr(L, "slhip_sample_actions"):
             L.slhip_sample_actions.argtypes = [_p, C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, _p, _p]
+        L.slhip_render_boards.argtypes = [C.POINTER(RenderArgs), _p]
+        L.slhip_env_render.argtypes = [C.POINTER(EnvBatch), _p, C.c_int, C.c_int, C.c_int, _p, _p, _p]
         L.slhip_obs_to_policy.argtypes = [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]
         L.slhip_gather_unique_id.argtypes = [_p]
         L.slhip_gather_init.argtypes = [_p, C.c_int, C.c_int, C.POINTER(_p)]

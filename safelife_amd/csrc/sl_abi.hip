@@ -1586,6 +1586,47 @@ int slhip_env_obs(const sl_env_batch *env, void *stream) {
     return err == hipSuccess ? SL_OK : hip_fail(err, "env_obs launch");
 }
 
+int slhip_render_boards(const sl_render_args *args, void *stream) {
+    if (!args) return fail(SL_E_ARG, "null render arguments");
+    const sl_render_args &a = *args;
+    if (a.N <= 0) return fail(SL_E_ARG, "render: N must be positive");
+    if (a.H < 1 || a.W < 1 || (long long)a.H * a.W > SL_MAX_CELLS) return fail(SL_E_SHAPE, "render: board shape outside 1..SL_MAX_CELLS cells");
+    if (!a.board || !a.goals || !a.sprites || !a.out) return fail(SL_E_ARG, "render: null pointer");
+    if (a.n_source < 1 || (!a.index && a.n_source < a.N)) return fail(SL_E_ARG, "render: n_source smaller than the frames read");
+    if (a.board_stride < 0 || a.goal_stride < 0) return fail(SL_E_ARG, "render: negative stride");
+    if (a.view_h < 0 || a.view_w < 0 || (a.view_h == 0) != (a.view_w == 0))
+        return fail(SL_E_ARG, "render: a view needs both sides positive (0 x 0: the whole board)");
+    if ((long long)a.view_h * a.view_w > SL_MAX_CELLS) return fail(SL_E_SHAPE, "render: view larger than SL_MAX_CELLS cells");
+    if (a.view_h > 0) {
+        if (!a.centers || a.center_stride < 2) return fail(SL_E_ARG, "render: a view needs centers (center_stride >= 2)");
+        if (a.exits && a.E < 1) return fail(SL_E_ARG, "render: exits with E < 1");
+    }
+    if (((uintptr_t)a.sprites & 15) || ((uintptr_t)a.out & 3))
+        return fail(SL_E_ARG, "render: sprites must be 16-byte aligned, out 4-byte aligned");
+    static const int variant = [] {          // A/B runs of the two kernel variants (sl_render.hip)
+        const char *e = getenv("SAFELIFE_RENDER_VARIANT");
+        return !e ? 0 : (!strcmp(e, "direct") ? 1 : (!strcmp(e, "stage") ? 2 : 0));
+    }();
+    const hipError_t err = sl::launch_render(a, variant, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "render launch");
+}
+
+int slhip_env_render(const sl_env_batch *env, const int32_t *env_ids, int n, int view_h, int view_w,
+                     const float *sprites, uint8_t *out, void *stream) {
+    if (!env) return fail(SL_E_ARG, "null env");
+    if (!env->board || !env->goals || !env->exit_locs || !env->scalars) return fail(SL_E_ARG, "null pointer in sl_env_batch");
+    if (env->B < 1 || env->E < 1) return fail(SL_E_ARG, "render: empty batch or E < 1");
+    if (!env_ids && n > env->B) return fail(SL_E_ARG, "render: more frames than envs");
+    sl_render_args a = {};
+    a.N = n, a.H = env->H, a.W = env->W, a.n_source = env->B;
+    a.view_h = view_h, a.view_w = view_w, a.E = env->E, a.aux_by_index = 1;
+    a.board_stride = a.goal_stride = (long long)env->H * env->W;
+    a.center_stride = sizeof(sl_env_scalars) / sizeof(int32_t);
+    a.board = env->board, a.goals = env->goals, a.index = env_ids, a.sprites = sprites;
+    a.centers = &env->scalars->agent_row, a.exits = env->exit_locs, a.out = out;
+    return slhip_render_boards(&a, stream);
+}
+
 int slhip_sample_actions(const float *probs, int B, int n_actions, unsigned long long seed, unsigned long long counter,
                          int32_t *actions, void *stream) {
     if (B < 0 || n_actions < 1 || n_actions > 64) return fail(SL_E_ARG, "bad sizes");

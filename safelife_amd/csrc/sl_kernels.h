@@ -73,6 +73,8 @@ size_t emd_workspace_bytes(int H, int W, int concurrency);
 hipError_t launch_emd(const sl_episode_queue &q, int H, int W, int num_samples, const int32_t *counts,
                       const uint16_t *keys, const uint8_t *type_masks, const double *ground, double penalty,
                       void *workspace, int concurrency, double *scores, int32_t *n_cells, hipStream_t stream);
+// sl_render.hip : boards -> RGB frames (variant: 0 the default, 1 cells decoded by every lane, 2 cells staged in LDS)
+hipError_t launch_render(const sl_render_args &args, int variant, hipStream_t stream);
 // envs [e_first, e_first + e_count) of the batch; actions / reward_t / done_t are indexed [t * tstride + e]
 // with the env's index in the whole batch
 // (sl_aql.hip dispatches the same kernel from queues of the library's own: PreparedStep below)

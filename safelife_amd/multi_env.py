@@ -173,6 +173,14 @@ class SafeLifeMultiAgentVectorEnv(object):
         self.base.steps_dispatched += 1
         return self.obs, self.reward, self.done, self.info
 
+    def render(self, env_ids=None, view_size=None, out=None):
+        """``SafeLifeVectorEnv.render`` for the boards of this batch; a view is centred on agent 0 (``render_game``
+        takes ``agent_locs[0]``)."""
+        from . import render
+        self.base._settle()
+        return render.render_envs(self.base, env_ids, view_size, out, centers=self.t["agents"],
+                                  center_stride=self.n_agents * 12)
+
     def side_effects_flush(self, overlap=False, defer=False):
         """The base env's ``side_effects_flush()`` over the episodes this env queued (one entry per env episode; the
         returned batch's ``agent_records()`` has every agent's record of the step that ended it)."""

@@ -21,8 +21,10 @@ kernel consumes draws in the reference's order, and the advanced state is
 written back into the generator, so results *and* generator state afterwards
 are identical to the reference.  Only PCG64 (numpy's default) is supported.
 
+* ``_render_board(board, goals, sprites)``                    module.c:438-512
+
 Not provided (out of the hot path): gen_pattern,
-wrapped_label, render_board.
+wrapped_label.
 """
 import ctypes as C
 
@@ -256,3 +258,19 @@ def execute_actions(board, locations, actions):
     np.copyto(board, _to_host(d_board, np.uint16)[0], casting="unsafe")
     np.copyto(locations, _to_host(d_locs, np.int64)[0].reshape(locations.shape), casting="unsafe")
     return None
+
+
+def _render_board(board, goals, sprites):
+    """uint8 [..., H*14, W*14, 3] RGB frames of uint16 boards [..., H, W] over their goals; ``sprites``: the float32
+    sheet, 70*70*4 values (module.c:438-512; safelife_amd.render has the arithmetic)."""
+    from . import render
+    b = np.ascontiguousarray(np.asarray(board).astype(np.uint16, copy=False))
+    g = np.ascontiguousarray(np.asarray(goals).astype(np.uint16, copy=False))
+    s = np.ascontiguousarray(np.asarray(sprites).astype(np.float32, copy=False))
+    if b.ndim < 2:
+        raise ValueError("Board must have at least two dimensions.")
+    if b.size != g.size:
+        raise ValueError("Board and goals must have same size.")
+    if s.size != 70 * 70 * 4:
+        raise ValueError("Sprites should have shape (70, 70, 4).")
+    return render.render_board(b, g.reshape(b.shape), None, s)

@@ -1140,6 +1140,16 @@ class SafeLifeVectorEnv(object):
         self._caller_ahead = True
         return self.obs
 
+    def render(self, env_ids=None, view_size=None, out=None):
+        """RGB frames of the envs' current state (all, or ``env_ids``), uint8 device tensor ``[n, vh*14, vw*14, 3]``:
+        the whole board, or ``view_size`` centred on the agent as ``render_game`` draws it (safelife_amd.render).
+        Ordered like ``get_obs()``: after the steps dispatched so far, queues and slices included."""
+        from . import render
+        self._settle()
+        frames = render.render_envs(self, env_ids, view_size, out)
+        self._caller_ahead = True
+        return frames
+
     def policy_obs(self, channels=_DEFAULT_CHANNELS, dtype=None, out=None):
         """The observation as the policy network takes it (training/models.py:100-103): channel-first,
         spatial axes swapped, ``[B, C, view_w, view_h]``, uint8 or float32 -- unpacked on the device from
