@@ -651,9 +651,18 @@ int slhip_obs_to_policy(const uint32_t *view, int B, int vh, int vw, const int32
 
 /* One categorical draw per env from policy probabilities, on the device, written as the int32 action the step kernels
  * read (training/ppo.py:66-69 draws on the host with numpy; there is no random stream to be compatible with).
- * probs: float32 [B, n_actions] (rows sum to 1); the draw of env e in call `counter` of a run seeded `seed` is a
- * function of (seed, counter, e) alone -- splitmix64, 24-bit uniform, inverse CDF -- so runs are reproducible and
- * shards may use their global env indices through `seed`. */
+ * probs: float32 [B, n_actions] (rows sum to 1), n_actions in 1..64; the draw of env e in call `counter` of a run
+ * seeded `seed` is a function of (seed, counter, e) alone, so runs are reproducible:
+ *   z = seed + G * (counter * 0x100000001B3 + e + 1) mod 2^64, G = 0x9E3779B97F4A7C15, through splitmix64's finalizer;
+ *   u = (z >> 40) * 2^-24, a 24-bit uniform in [0, 1 - 2^-24];
+ *   cum_k = the fp32 running sum p_0 + ... + p_k over all n_actions entries, in index order;
+ *   the action is the first k with u < cum_k; if there is none, the largest k with p_k > 0; if no entry is positive,
+ *   n_actions - 1.
+ * An action with p_k == 0 is therefore never returned while any entry is positive (a row whose fp32 sum stays below 1
+ * gives what rounding leaves to its last POSITIVE action), and the result lies in [0, n_actions) for rows with NaN,
+ * inf or negative entries as well (which action they get is otherwise unspecified).
+ * A caller that holds envs [lo, lo + B) of a larger batch passes seed + G * lo (mod 2^64) and draws exactly what envs
+ * lo + e of the whole batch draw under `seed`; seed + lo does NOT do that. */
 int slhip_sample_actions(const float *probs, int B, int n_actions, unsigned long long seed, unsigned long long counter,
                          int32_t *actions, void *stream);
 

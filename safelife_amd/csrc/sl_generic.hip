@@ -986,8 +986,13 @@ __global__ __launch_bounds__(256) void k_obs_to_policy(const u32 *__restrict__ v
 // ------------------------------------------------------------------------------ launchers
 
 // One categorical draw per env from the policy's probabilities (training/ppo.py:66-69 draws on the host with numpy):
-// u = a 24-bit uniform from splitmix64(seed, counter, env), the action = the first k with u < p_0 + ... + p_k (the last
-// action takes what rounding leaves).  One thread per env; the result goes straight into the int32 buffer the step reads.
+// u = a 24-bit uniform from splitmix64(seed, counter, env); cum_k = the fp32 running sum p_0 + ... + p_k over ALL A
+// entries, in index order.  The action is the first k with u < cum_k; if there is none (the fp32 sum of a row can stay
+// below 1 while u reaches 1 - 2^-24), the largest k with p_k > 0, which takes what rounding leaves; A-1 only when no
+// entry is positive.  So an action of probability zero is never drawn while any entry is positive, and the result is
+// in [0, A) whatever the row holds (NaN, inf, negative entries).  z = seed + G * (counter * K + e + 1): a caller that
+// holds envs [lo, hi) of a larger batch passes seed + G * lo (mod 2^64) and gets the draws of envs lo + e of the whole.
+// One thread per env; the result goes straight into the int32 buffer the step reads.
 __global__ __launch_bounds__(256) void k_sample_actions(const float *__restrict__ probs, int B, int A, unsigned long long seed,
                                                         unsigned long long counter, int32_t *__restrict__ actions) {
     const int e = blockIdx.x * 256 + threadIdx.x;
@@ -999,9 +1004,11 @@ __global__ __launch_bounds__(256) void k_sample_actions(const float *__restrict_
     const float u = (float)(unsigned)(z >> 40) * (1.0f / 16777216.0f);
     const float *p = probs + (size_t)e * A;
     float cum = 0.0f;
-    int a = A - 1;
-    for (int k = 0; k < A - 1; ++k) {
-        cum += p[k];
+    int a = A - 1;                  // the largest k with p_k > 0 seen so far (A-1 while there is none)
+    for (int k = 0; k < A; ++k) {
+        const float pk = p[k];
+        cum += pk;
+        if (pk > 0.0f) a = k;
         if (u < cum) {
             a = k;
             break;

@@ -20,6 +20,8 @@ import collections
 
 StepResult = collections.namedtuple("StepResult", "obs actions rewards done next_obs agent_ids policies values")
 
+_SPLITMIX_G = 0x9E3779B97F4A7C15        # the increment of the draw kernel's splitmix64 (slhip_sample_actions)
+
 
 class VectorRunner(object):
     """
@@ -104,6 +106,12 @@ class PipelinedRunner(object):
     group's part of the ONE int32 action tensor the step kernel reads); ``sampler="torch"`` uses ``torch.multinomial``
     and a copy instead (20 times the device time at 8192 envs).
 
+    With the device sampler the action of an env at a step is a function of ``(seed, step, global env index)`` and its
+    probabilities alone, the global index being ``env.env_offset + e``: the same run cut into another number of slices,
+    or dealt to shards with their own ``env_offset``, draws the same actions for the same envs.  (A group that holds
+    envs ``[lo, hi)`` calls the kernel with ``seed + G * (env_offset + lo) mod 2**64``, ``G`` the kernel's splitmix64
+    increment, and its own step count as the counter.)
+
     Parameters: `env` built with ``policy_layout=...``, ``auto_reset=True``, ``slices >= 2``.
     ``policy(obs [n,C,W,H]) -> (values, probs float32 [n,9])`` gets the env's policy tensor AS IT IS (uint8 or
     float32: a network casts its own input, a cheap policy need not pay for a float copy of the observation).
@@ -121,6 +129,7 @@ class PipelinedRunner(object):
             raise ValueError("sampler must be 'device' or 'torch'")
         self.env, self.policy, self.on_step, self.sampler, self.generator = env, policy, on_step, sampler, generator
         self.seed = int(seed) & (2 ** 64 - 1)
+        offset = int(env.env_offset)
         self.actions = torch.zeros(env.num_envs, dtype=torch.int32, device=env.device)
         self.num_steps = 0
         self._group_steps = [0] * env.slices        # steps taken per group: the draw counter of the group's next step
@@ -130,8 +139,10 @@ class PipelinedRunner(object):
         for g in range(env.slices):
             lo, hi = env.slice_bounds[g], env.slice_bounds[g + 1]
             st = env.slice_stream(g)
+            # (the kernel's env e of this group is env offset + lo + e of the whole run: see slhip_sample_actions)
             self._groups.append((g, lo, hi, st, torch.cuda.stream(st), env.policy_tensor[lo:hi],
-                                 self.actions.data_ptr() + 4 * lo, st.cuda_stream))
+                                 self.actions.data_ptr() + 4 * lo, st.cuda_stream,
+                                 (self.seed + _SPLITMIX_G * (offset + lo)) & (2 ** 64 - 1)))
 
     def start(self):
         if not self._started:
@@ -141,7 +152,7 @@ class PipelinedRunner(object):
 
     def step_group(self, g):
         torch, env = self.torch, self.env
-        g, lo, hi, st, ctx, obs, act_ptr, st_ptr = self._groups[g]
+        g, lo, hi, st, ctx, obs, act_ptr, st_ptr, group_seed = self._groups[g]
         if hi <= lo:
             return
         # Work the caller put on ITS stream since the last fence (env.reset(mask), step(), a snapshot ...) is fenced HERE,
@@ -159,9 +170,8 @@ class PipelinedRunner(object):
             if self.sampler == "device":
                 if probs.dtype != torch.float32 or not probs.is_contiguous():
                     probs = probs.to(torch.float32).contiguous()
-                # (seed offset by the group's first env: every env of the batch has its own draw per step)
-                rc = self._lib.slhip_sample_actions(probs.data_ptr(), hi - lo, probs.shape[1], (self.seed + lo) & (2 ** 64 - 1),
-                                                    draw, act_ptr, st_ptr)
+                rc = self._lib.slhip_sample_actions(probs.data_ptr(), hi - lo, probs.shape[1], group_seed, draw, act_ptr,
+                                                    st_ptr)
                 if rc:
                     self._hip.check(rc)
             else:

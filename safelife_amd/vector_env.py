@@ -236,7 +236,8 @@ class SafeLifeVectorEnv(object):
     first_level : int or array     pool index loaded by env e at its first reset
                                    (default ``(env_offset + e) % len(pool)``)
     level_stride : int             an env's next level is ``(level + level_stride) % len(pool)``
-    env_offset : int               global index of this process's env 0 (multi-GPU sharding)
+    env_offset : int               global index of this process's env 0 (multi-GPU sharding); kept as
+                                   ``env.env_offset`` (``PipelinedRunner`` draws actions by global index)
     with_obs : bool                False skips observation writes entirely
     slices : int                   >1: the batch is cut into this many contiguous slices, each stepped by its
                                    own launch on its own HIP stream (``slhip_env_step_slices``; the streams are
@@ -294,6 +295,7 @@ class SafeLifeVectorEnv(object):
         self.pool = pool
         self.device = _hip.device()
         self.num_envs = B = int(num_envs)
+        self.env_offset = int(env_offset)
         H, W = pool.shape
         E = pool.exit_slots
         self.view_shape = tuple(int(v) for v in view_shape)
