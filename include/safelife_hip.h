@@ -472,7 +472,10 @@ int slhip_queues_selftest(void *handle, int what, int arg);
  *                ascending order (np.unique), 0xFFFF-padded (more than SL_SE_MAX_KEYS-8 of them: the rest are cut)
  *   life_dist    double [C,2,8,H,W]  out: counts / num_samples as float64 (num_runs = 1), colour-major
  *   type_masks   uint8  [C,2,SL_SE_MAX_KEYS-8,H,W] out: (b0 == key), (final board == key) for slots 8..
- * Supported for the board shapes of the row kernels (elsewhere SL_E_UNSUPPORTED: use the primitives). */
+ * Any board of 3 <= H, W with H*W <= 4096 cells (so every shape up to 64x64): the row kernels where the shape has
+ * them and work_boards / queue->boards are 16-byte aligned, else (other shapes, unaligned boards,
+ * SAFELIFE_HIP_FORCE_GENERIC=1) the size-generic kernels, with bit-identical results.  Larger boards:
+ * SL_E_UNSUPPORTED (use the primitives). */
 #define SL_SE_MAX_KEYS 24
 int slhip_side_effects(const sl_env_batch *env, const sl_episode_queue *queue, int num_samples, int derive_streams,
                        uint16_t *work_boards, float *work_prob, int32_t *work_steps, sl_pcg64 *work_rng,

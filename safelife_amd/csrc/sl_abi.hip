@@ -314,12 +314,23 @@ int slhip_life_occupancy(const uint16_t *in, int32_t *counts, int B, int H, int 
     const sl::Jump *jump;
     if ((rc = jump_table(&jump))) return rc;
     // 16-bit (or drained 8-bit) per-colour counters in LDS: the row kernel covers every step count the
-    // reference is called with
-    hipError_t err = (sl::rowlane_supports(H, W) && n_steps <= 65535 && !force_generic())
-                         ? sl::launch_occupancy_rowlane(in, counts, (size_t)H * W * 8, B, nullptr, 0, nullptr, H, W, spawn_prob,
-                                                        n_steps, rng, jump, (hipStream_t)stream)
-                         : sl::launch_advance_generic(in, nullptr, B, H, W, spawn_prob, n_steps, rng, jump, counts,
-                                                      (hipStream_t)stream);
+    // reference is called with.  Other shapes count in global memory (k_advance_generic): the LDS-counter kernel of
+    // the side-effect pass (k_occupancy_generic) measured 5 % faster on 13x17 and 17 % slower on 33x64 boards
+    // (profiles/occupancy_generic_bench.json), so it is not taken here.  SL_LIFE_OCCUPANCY_LDS is the timing-only
+    // build that measurement compares (tools/occupancy_generic_bench.py), like SL_OCC_NODRAW in sl_rowlane.hip.
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t board_counts = (size_t)H * W * 8;
+    hipError_t err;
+    if (sl::rowlane_supports(H, W) && n_steps <= 65535 && !force_generic())
+        err = sl::launch_occupancy_rowlane(in, counts, board_counts, B, nullptr, 0, nullptr, H, W, spawn_prob, n_steps, rng,
+                                           jump, st);
+#ifdef SL_LIFE_OCCUPANCY_LDS
+    else if (sl::occupancy_generic_supports(H, W, n_steps))
+        err = sl::launch_occupancy_generic(in, counts, board_counts, B, nullptr, 0, nullptr, H, W, spawn_prob, n_steps, rng,
+                                           jump, st);
+#endif
+    else
+        err = sl::launch_advance_generic(in, nullptr, B, H, W, spawn_prob, n_steps, rng, jump, counts, st);
     return err == hipSuccess ? SL_OK : hip_fail(err, "life_occupancy launch");
 }
 
@@ -1410,33 +1421,40 @@ int slhip_side_effects(const sl_env_batch *env, const sl_episode_queue *queue, i
         !counts || !keys || !life_dist || !type_masks)
         return fail(SL_E_ARG, "null pointer");
     const int H = env->H, W = env->W, C = queue->capacity;
-    if (!sl::rowlane_supports(H, W) || force_generic() || (((uintptr_t)work_boards | (uintptr_t)queue->boards) & 15))
-        return fail(SL_E_UNSUPPORTED, "side-effect pass: board shape without row kernels (or unaligned boards)");
+    // Row kernels where the shape has them and the boards are 16-byte aligned; every other board of up to 4096 cells
+    // (any 3 <= H, W <= 64, unaligned boards, SAFELIFE_HIP_FORCE_GENERIC=1) takes the size-generic kernels: the same
+    // launches, the same contract (device-side count, pre-roll, two runs), bit-identical results.
+    const bool rows = sl::rowlane_supports(H, W) && !force_generic() &&
+                      !(((uintptr_t)work_boards | (uintptr_t)queue->boards) & 15);
+    if (!rows && !sl::occupancy_generic_supports(H, W, num_samples))
+        return fail(SL_E_UNSUPPORTED, "side-effect pass: board of more than 4096 cells");
     const sl::Jump *jump;
     if ((rc = jump_table(&jump))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t board_counts = (size_t)H * W * 8;
+    auto occupancy = [&](const uint16_t *in, int32_t *out, int B, int period, const int32_t *pre) {
+        return rows ? sl::launch_occupancy_rowlane(in, out, board_counts, B, queue->count, period, pre, H, W, work_prob,
+                                                   num_samples, work_rng, jump, st)
+                    : sl::launch_occupancy_generic(in, out, board_counts, B, queue->count, period, pre, H, W, work_prob,
+                                                   num_samples, work_rng, jump, st);
+    };
     hipError_t err;
     if (derive_streams) {
         // one fused launch over two runs of C boards: [roll b0 forward num_steps, then sample] and [sample the final
         // boards], every board with a stream of its own -- a chain of num_steps + num_samples CA steps instead of
         // num_steps + 2 * num_samples, and twice the wavefronts in flight
         err = sl::launch_se_gather(*env, *queue, work_boards, work_prob, work_steps, work_rng, true, st);
-        if (err == hipSuccess)
-            err = sl::launch_occupancy_rowlane(work_boards, counts, board_counts, 2 * C, queue->count, C, work_steps, H, W,
-                                               work_prob, num_samples, work_rng, jump, st);
+        if (err == hipSuccess) err = occupancy(work_boards, counts, 2 * C, C, work_steps);
     } else {
         // the reference's order on ONE generator per entry: roll-forward, inaction tensor, action tensor
         err = sl::launch_se_gather(*env, *queue, work_boards, work_prob, work_steps, nullptr, false, st);
         if (err == hipSuccess)
-            err = sl::launch_advance_rowlane(work_boards, work_boards, C, H, W, work_prob, 0, work_steps, queue->count,
-                                             work_rng, jump, st);
-        if (err == hipSuccess)
-            err = sl::launch_occupancy_rowlane(work_boards, counts, board_counts, C, queue->count, 0, nullptr, H, W,
-                                               work_prob, num_samples, work_rng, jump, st);
-        if (err == hipSuccess)
-            err = sl::launch_occupancy_rowlane(queue->boards, counts + (size_t)C * board_counts, board_counts, C,
-                                               queue->count, 0, nullptr, H, W, work_prob, num_samples, work_rng, jump, st);
+            err = rows ? sl::launch_advance_rowlane(work_boards, work_boards, C, H, W, work_prob, 0, work_steps, queue->count,
+                                                    work_rng, jump, st)
+                       : sl::launch_advance_generic(work_boards, work_boards, C, H, W, work_prob, 0, work_rng, jump, nullptr,
+                                                    st, work_steps, queue->count);
+        if (err == hipSuccess) err = occupancy(work_boards, counts, C, 0, nullptr);
+        if (err == hipSuccess) err = occupancy(queue->boards, counts + (size_t)C * board_counts, C, 0, nullptr);
     }
     if (err == hipSuccess)
         err = sl::launch_se_distributions(*env, *queue, counts, (double)num_samples, keys, life_dist, type_masks, st);

@@ -122,14 +122,18 @@ size_t generic_lds_bytes(int HW, int nbuf) { return 128 + (size_t)nbuf * ((HW + 
 
 // ------------------------------------------------------------------ advance_board / occupancy
 
+// (`out` may be `in`: a board is staged into LDS in full before anything of it is stored, and no thread reads `in`
+//  after the first barrier -- the side-effect pass rolls its work boards forward in place)
 __global__ __launch_bounds__(GB_MAX) void k_advance_generic(const u16 *__restrict__ in, u16 *__restrict__ out,
                                                         int H, int W, const float *__restrict__ spawn_prob,
                                                         int n_steps, sl_pcg64 *rng,
                                                         const Jump *__restrict__ jump,
                                                         int32_t *__restrict__ occupancy,
-                                                        const int32_t *__restrict__ n_each) {
+                                                        const int32_t *__restrict__ n_each,
+                                                        const int32_t *__restrict__ n_valid) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int HW = H * W, b = blockIdx.x, tid = threadIdx.x;
+    if (n_valid && b >= *n_valid) return;       // only the first *n_valid boards exist (workgroup-uniform)
     if (n_each) n_steps = n_each[b];            // per-board step counts (workgroup-uniform)
     GenericLds l = carve(smem, HW, 3);
     const u16 *src = in + (size_t)b * HW;
@@ -159,6 +163,68 @@ __global__ __launch_bounds__(GB_MAX) void k_advance_generic(const u16 *__restric
         u16 *dst = out + (size_t)b * HW;
         for (int i = tid; i < HW; i += GB) dst[i] = cur[i];
     }
+    if (tid < 4) ((u64 *)(rng + b))[tid] = l.rng[tid];
+}
+
+// life_occupancy (advance_board.c:153-189) for any board of up to OCC_MAX_CELLS cells, the counters on chip: next to
+// the three board buffers of ca_step_block the workgroup keeps one uint16 counter per cell and colour in LDS, colour-
+// major ([8][cells]: the lanes of a wavefront tick neighbouring halfwords), and the step loop touches no global memory.
+// After each step a cell that is ALIVE and not AGENT|EXIT|FROZEN ticks the counter of its colour (bits 9-11): states
+// 1..n_steps count, the input does not.  A cell belongs to one thread for the whole launch (i = tid + k * GB), so the
+// tick is a plain read-modify-write of that thread's own halfword.
+// The counters cannot wrap: a cell ticks at most one counter once per counted step, and the launcher admits at most
+// 65535 counted steps (the ABI's bound on num_samples; slhip_life_occupancy routes larger n_steps elsewhere), so no
+// counter exceeds 65535 = the largest uint16.  They are widened into the int32 [H,W,8] output once, at the end.
+// The contract of launch_occupancy_rowlane: boards come in runs of valid_period (0: one run of B), of which the first
+// min(*n_valid, valid_period) exist -- a workgroup past that does nothing and writes nothing; pre_steps[b] uncounted CA
+// steps run first on the same generator (advance_board(b0, p, num_steps), side_effects.py:108).  Every loop bound is
+// the board's size or a step count all threads of the workgroup share: no barrier is reached by part of a workgroup.
+constexpr int OCC_MAX_CELLS = 4096;     // 128 + 22 bytes per cell: 90240 bytes of LDS at 64x64
+
+static size_t occupancy_lds_bytes(int HW) { return generic_lds_bytes(HW, 3) + (size_t)8 * ((HW + 7) & ~7) * sizeof(u16); }
+
+__global__ __launch_bounds__(GB_MAX) void k_occupancy_generic(const u16 *__restrict__ in, int32_t *__restrict__ counts,
+                                                          size_t counts_stride, int B, const int32_t *__restrict__ n_valid,
+                                                          int valid_period, const int32_t *__restrict__ pre_steps,
+                                                          int H, int W, const float *__restrict__ spawn_prob, int n_steps,
+                                                          sl_pcg64 *rng, const Jump *__restrict__ jump) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int HW = H * W, hwp = (HW + 7) & ~7, b = blockIdx.x, tid = threadIdx.x;
+    const int period = valid_period > 0 ? valid_period : B;
+    const int run = b / period, in_run = b - run * period;
+    int run_len = min(period, B - run * period);
+    if (n_valid) run_len = min(run_len, *n_valid);
+    if (in_run >= run_len) return;              // (workgroup-uniform, ahead of every barrier)
+    GenericLds l = carve(smem, HW, 3);
+    u16 *cnt = l.buf[0] + (size_t)3 * hwp;      // [8][hwp], behind the three board buffers
+    const u16 *src = in + (size_t)b * HW;
+    for (int i = tid; i < HW; i += GB) l.buf[0][i] = src[i];
+    for (int i = tid; i < 4 * hwp; i += GB) ((u32 *)cnt)[i] = 0u;
+    if (tid < 4) l.rng[tid] = ((const u64 *)(rng + b))[tid];
+    __syncthreads();
+    const float inv_w = 1.0f / (float)W;
+    const double p = (double)spawn_prob[b];
+    const int pre = pre_steps ? max(0, pre_steps[b]) : 0;
+    const int end = pre + n_steps;
+    u16 *cur = l.buf[0], *nxt = l.buf[2];
+    for (int s = 0; s < end; ++s) {
+        ca_step_block(cur, l.buf[1], nxt, H, W, inv_w, p, l.rng, jump, l.wave_tot);
+        if (s >= pre) {
+            for (int i = tid; i < HW; i += GB) {
+                const u32 c = nxt[i];
+                if ((c & ALIVE) && !(c & (AGENT | EXIT | FROZEN))) {
+                    u16 *k = cnt + (size_t)((c >> 9) & 7) * hwp + i;
+                    *k = (u16)(*k + 1);
+                }
+            }
+        }
+        u16 *t = cur;
+        cur = nxt;
+        nxt = t;
+    }
+    __syncthreads();                            // the counters are read back by other threads than their owners
+    int32_t *dst = counts + (size_t)b * counts_stride;
+    for (int j = tid; j < HW * 8; j += GB) dst[j] = cnt[(size_t)(j & 7) * hwp + (j >> 3)];
     if (tid < 4) ((u64 *)(rng + b))[tid] = l.rng[tid];
 }
 
@@ -1041,12 +1107,29 @@ static hipError_t set_lds(const void *fn, size_t bytes) {
 
 hipError_t launch_advance_generic(const u16 *in, u16 *out, int B, int H, int W, const float *spawn_prob,
                                   int n_steps, sl_pcg64 *rng, const Jump *jump, int32_t *occupancy,
-                                  hipStream_t stream, const int32_t *n_each) {
+                                  hipStream_t stream, const int32_t *n_each, const int32_t *n_valid) {
     size_t lds = generic_lds_bytes(H * W, 3);
     hipError_t err = set_lds((const void *)k_advance_generic, lds);
     if (err != hipSuccess) return err;
     hipLaunchKernelGGL(k_advance_generic, dim3(B), dim3(generic_threads(H * W)), lds, stream, in, out, H, W, spawn_prob,
-                       n_steps, rng, jump, occupancy, n_each);
+                       n_steps, rng, jump, occupancy, n_each, n_valid);
+    return hipGetLastError();
+}
+
+bool occupancy_generic_supports(int H, int W, int n_steps) {
+    return H >= 3 && W >= 3 && (long long)H * W <= OCC_MAX_CELLS && n_steps >= 0 && n_steps <= 65535;
+}
+
+hipError_t launch_occupancy_generic(const u16 *in, int32_t *counts, size_t counts_stride, int B, const int32_t *n_valid,
+                                    int valid_period, const int32_t *pre_steps, int H, int W, const float *spawn_prob,
+                                    int n_steps, sl_pcg64 *rng, const Jump *jump, hipStream_t stream) {
+    if (!occupancy_generic_supports(H, W, n_steps)) return hipErrorInvalidValue;    // (uint16 counters, 160 KB of LDS)
+    if (B <= 0) return hipSuccess;
+    const size_t lds = occupancy_lds_bytes(H * W);
+    hipError_t err = set_lds((const void *)k_occupancy_generic, lds);
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL(k_occupancy_generic, dim3(B), dim3(generic_threads(H * W)), lds, stream, in, counts, counts_stride, B,
+                       n_valid, valid_period, pre_steps, H, W, spawn_prob, n_steps, rng, jump);
     return hipGetLastError();
 }
 

@@ -12,7 +12,13 @@ size_t generic_lds_bytes(int HW, int nbuf);
 // sl_generic.hip : one workgroup per board, any 3 <= H, W with H*W <= SL_MAX_CELLS
 hipError_t launch_advance_generic(const u16 *in, u16 *out, int B, int H, int W, const float *spawn_prob,
                                   int n_steps, sl_pcg64 *rng, const Jump *jump, int32_t *occupancy,
-                                  hipStream_t stream, const int32_t *n_each = nullptr);
+                                  hipStream_t stream, const int32_t *n_each = nullptr, const int32_t *n_valid = nullptr);
+// life_occupancy with the counters in LDS (uint16 per cell and colour): boards of up to 4096 cells, n_steps <= 65535;
+// the arguments of launch_occupancy_rowlane below, same meaning
+bool occupancy_generic_supports(int H, int W, int n_steps);
+hipError_t launch_occupancy_generic(const u16 *in, int32_t *counts, size_t counts_stride, int B, const int32_t *n_valid,
+                                    int valid_period, const int32_t *pre_steps, int H, int W, const float *spawn_prob,
+                                    int n_steps, sl_pcg64 *rng, const Jump *jump, hipStream_t stream);
 hipError_t launch_alive_counts(const u16 *board, const u16 *goals, int B, int HW, int64_t *out,
                                hipStream_t stream);
 hipError_t launch_execute_actions(u16 *board, int B, int H, int W, int64_t *locs, const int64_t *actions,

@@ -265,7 +265,8 @@ class SafeLifeVectorEnv(object):
                                    ends (record + the board as the agent left it, taken before an auto-reset
                                    reloads the slot) and ``side_effects_flush()`` runs the episode-end pass of the
                                    reference's ``side_effect_score`` over the queue on the device -- see
-                                   ``SideEffectBatch``.  ``capacity``: episodes held between two flushes; ``keep``
+                                   ``SideEffectBatch``; any pool shape from 3x3 to 64x64 (shapes without row
+                                   kernels take the size-generic pass).  ``capacity``: episodes held between two flushes; ``keep``
                                    (default 2): output sets cycled -- a batch's tensors are overwritten by the
                                    ``keep``-th flush after it.
     wrappers : dict or None        training-wrapper math of the reference's env_wrappers.py, fused into the
