@@ -709,6 +709,59 @@ int slhip_render_boards(const sl_render_args *args, void *stream);
 int slhip_env_render(const sl_env_batch *env, const int32_t *env_ids, int n, int view_h, int view_w,
                      const float *sprites, uint8_t *out, void *stream);
 
+/* ---- PPO training batches: the rollout buffer and its returns / GAE advantages (additive to ABI 13: two new symbols and
+ * one new struct, nothing existing changes, so SL_ABI_VERSION stays where it is) ---------------------------------------
+ * What the reference's PPO.gen_training_batch (training/ppo.py:74-143) does with the tuples of take_one_step, on the
+ * device: a window of T steps of B envs is kept TIME-MAJOR ([T,B]: row t holds step t of every env), and one kernel
+ * turns it into discounted returns and GAE advantages, bit exact with numpy's arithmetic in the reference.
+ * The struct lives on the HOST; every pointer inside is a device pointer the caller owns.
+ *
+ * The arithmetic (numpy 2 promotion rules; g, l = gamma, lmda as doubles; f32(x) = x rounded to float32):
+ *   - a trajectory is the run of steps of one env between resets: it ends at a step with done != 0 and at the window's
+ *     last row.  It is CLOSED if its last step has done != 0 -- its final_value is then the Python float 0.0 -- else OPEN,
+ *     with final_value = final_values[b], float32 V(next_obs) of the window's last step;
+ *   - a trajectory is WIDE if it is closed or has one step (np.append(values[1:], final_value) is float64 then: a Python
+ *     float joins a float32 array, or anything joins an empty one), else NARROW;
+ *   - wide:    adv[i] = (f64(r[i]) + g * f64(v[i+1])) - f64(v[i]);  adv[i] += l * adv[i+1]; all float64, v[last+1] =
+ *              final_value;
+ *   - narrow, float32 rewards:  adv[i] = (r[i] + f32(g) * v[i+1]) - v[i];  adv[i] += f32(l) * adv[i+1]; all float32;
+ *   - narrow, float64 rewards:  adv[i] = (r[i] + f64(f32(g) * v[i+1])) - f64(v[i]);  adv[i] += l * adv[i+1]: the product
+ *              is still float32 (v is a float32 array), the rest float64;
+ *   - returns, in the rewards' dtype R: ret[last] = r[last] + R(f32(g) * final_value) (a float32 product even for float64
+ *     rewards; a closed trajectory adds 0.0);  ret[i] = r[i] + R(g) * ret[i+1];
+ *   - nothing is fused, and everything is rounded to float32 once, at the end. */
+#define SL_REWARD_F32 0
+#define SL_REWARD_F64 1
+#define SL_ROLLOUT_BAD_ACTION 1   /* bit of *status: a recorded action lay outside [0, n_actions) */
+typedef struct sl_rollout {       /* 80 bytes */
+    int32_t T, B;                 /* steps of the window, envs; both >= 1 */
+    int32_t reward_dtype;         /* SL_REWARD_F32 or SL_REWARD_F64: what `rewards` holds and the recorded rewards are */
+    int32_t reserved;
+    long long row_stride;         /* elements between rows t and t + 1 of the five arrays below, >= B */
+    long long out_stride;         /* the same for returns / advantages / traj_start of slhip_training_batch, >= B */
+    int32_t *actions;             /* [T, row_stride] */
+    float *action_prob;           /* [T, row_stride] probability the policy gave the action taken */
+    void *rewards;                /* [T, row_stride] float32 or float64 */
+    float *values;                /* [T, row_stride] V(obs) */
+    uint8_t *done;                /* [T, row_stride] != 0: the step ended the env's episode */
+    int32_t *status;              /* one device word, zeroed by the caller; the kernels only ever set bits (SL_ROLLOUT_*) */
+} sl_rollout;
+
+/* Step t of the window: row t of the five arrays takes actions[b], probs[b * n_actions + actions[b]], rewards[b]
+ * (buf->reward_dtype), values[b], done[b] -- one launch where a gather and four copies would run.  actions: int32 [B];
+ * probs: float32 [B, n_actions]; values: float32 [B]; done: uint8 [B].  An action outside [0, n_actions) reads no
+ * probability: 0 is recorded and SL_ROLLOUT_BAD_ACTION is raised in *buf->status (the action itself is kept). */
+int slhip_rollout_record(const sl_rollout *buf, int t, const int32_t *actions, const float *probs, int n_actions,
+                         const void *rewards, const float *values, const uint8_t *done, void *stream);
+
+/* Returns and advantages of the whole window by the rules above, from buf->rewards / values / done (the other pointers
+ * of *buf are not used).  final_values: float32 [B], V(next_obs) of the last step -- envs whose last step has `done` do
+ * not read theirs.  returns, advantages: float32 [T, out_stride]; traj_start: optional uint8 [T, out_stride] (NULL:
+ * skipped), 1 where step t is the first of its trajectory (t == 0 or done[t-1]) -- with it a caller can regroup the rows
+ * in the reference's trajectory order. */
+int slhip_training_batch(const sl_rollout *buf, const float *final_values, double gamma, double lmda, float *returns,
+                         float *advantages, uint8_t *traj_start, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,7 +31,10 @@ EXPORTS = (
     "slhip_queues_open", "slhip_queues_open_on", "slhip_queues_stream_shares", "slhip_gather_stream_shares", "slhip_gather_poke", "slhip_queues_mode", "slhip_queues_steps", "slhip_queues_step", "slhip_queues_stage", "slhip_queues_go", "slhip_queues_marker",
     "slhip_queues_wait", "slhip_queues_sync", "slhip_queues_close", "slhip_queues_selftest",
     "slhip_render_boards", "slhip_env_render",
+    "slhip_rollout_record", "slhip_training_batch",
 )
+REWARD_F32, REWARD_F64 = 0, 1
+ROLLOUT_BAD_ACTION = 1
 QUEUES_RELEASE_FREE = 1
 QUEUES_STAGE_MAX = 48
 QUEUES_SELFTEST_PLANT, QUEUES_SELFTEST_SWAP = 1, 2
@@ -141,6 +144,13 @@ class RenderArgs(C.Structure):
                 + [(n, C.c_void_p) for n in ("board", "goals", "index", "sprites", "orientation", "centers", "exits", "out")])
 
 
+class Rollout(C.Structure):
+    """struct sl_rollout (80 bytes)"""
+    _fields_ = ([(n, C.c_int32) for n in ("T", "B", "reward_dtype", "reserved")]
+                + [(n, C.c_longlong) for n in ("row_stride", "out_stride")]
+                + [(n, C.c_void_p) for n in ("actions", "action_prob", "rewards", "values", "done", "status")])
+
+
 class EnvBatch(C.Structure):
     _fields_ = (
         [(n, C.c_int32) for n in ENV_SCALARS_HEAD]
@@ -233,6 +243,8 @@ def lib():
             L.slhip_sample_actions.argtypes = [_p, C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, _p, _p]
         L.slhip_render_boards.argtypes = [C.POINTER(RenderArgs), _p]
         L.slhip_env_render.argtypes = [C.POINTER(EnvBatch), _p, C.c_int, C.c_int, C.c_int, _p, _p, _p]
+        L.slhip_rollout_record.argtypes = [C.POINTER(Rollout), C.c_int, _p, _p, C.c_int, _p, _p, _p, _p]
+        L.slhip_training_batch.argtypes = [C.POINTER(Rollout), _p, C.c_double, C.c_double, _p, _p, _p, _p]
         L.slhip_obs_to_policy.argtypes = [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]
         L.slhip_gather_unique_id.argtypes = [_p]
         L.slhip_gather_init.argtypes = [_p, C.c_int, C.c_int, C.POINTER(_p)]

@@ -1654,6 +1654,37 @@ int slhip_sample_actions(const float *probs, int B, int n_actions, unsigned long
     return err == hipSuccess ? SL_OK : hip_fail(err, "sample_actions launch");
 }
 
+static int check_rollout(const sl_rollout *buf) {
+    if (!buf) return fail(SL_E_ARG, "rollout: null buffer description");
+    if (buf->T < 1 || buf->B < 1) return fail(SL_E_ARG, "rollout: T and B must be at least 1");
+    if (buf->reward_dtype != SL_REWARD_F32 && buf->reward_dtype != SL_REWARD_F64)
+        return fail(SL_E_ARG, "rollout: reward_dtype must be SL_REWARD_F32 or SL_REWARD_F64");
+    if (buf->row_stride < buf->B) return fail(SL_E_ARG, "rollout: row_stride smaller than B");
+    if (!buf->rewards || !buf->values || !buf->done) return fail(SL_E_ARG, "rollout: null rewards / values / done");
+    return SL_OK;
+}
+
+int slhip_rollout_record(const sl_rollout *buf, int t, const int32_t *actions, const float *probs, int n_actions,
+                         const void *rewards, const float *values, const uint8_t *done, void *stream) {
+    if (int rc = check_rollout(buf)) return rc;
+    if (!buf->actions || !buf->action_prob || !buf->status) return fail(SL_E_ARG, "rollout: null actions / action_prob / status");
+    if (t < 0 || t >= buf->T) return fail(SL_E_ARG, "rollout_record: t outside [0, T)");
+    if (n_actions < 1) return fail(SL_E_ARG, "rollout_record: n_actions must be at least 1");
+    if (!actions || !probs || !rewards || !values || !done) return fail(SL_E_ARG, "rollout_record: null pointer");
+    const hipError_t err = sl::launch_rollout_record(*buf, t, actions, probs, n_actions, rewards, values, done, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "rollout_record launch");
+}
+
+int slhip_training_batch(const sl_rollout *buf, const float *final_values, double gamma, double lmda, float *returns,
+                         float *advantages, uint8_t *traj_start, void *stream) {
+    if (int rc = check_rollout(buf)) return rc;
+    if (buf->out_stride < buf->B) return fail(SL_E_ARG, "training_batch: out_stride smaller than B");
+    if (!final_values || !returns || !advantages) return fail(SL_E_ARG, "training_batch: null pointer");
+    const hipError_t err = sl::launch_training_batch(*buf, final_values, gamma, lmda, returns, advantages, traj_start,
+                                                     (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "training_batch launch");
+}
+
 int slhip_obs_to_policy(const uint32_t *view, int B, int vh, int vw, const int32_t *channels, int C, void *out,
                         int dtype, void *stream) {
     if (B < 0 || vh < 1 || vw < 1) return fail(SL_E_ARG, "bad view shape");

@@ -81,6 +81,11 @@ hipError_t launch_emd(const sl_episode_queue &q, int H, int W, int num_samples, 
                       void *workspace, int concurrency, double *scores, int32_t *n_cells, hipStream_t stream);
 // sl_render.hip : boards -> RGB frames (variant: 0 the default, 1 cells decoded by every lane, 2 cells staged in LDS)
 hipError_t launch_render(const sl_render_args &args, int variant, hipStream_t stream);
+// sl_rollout.hip : the rollout buffer's per-step record, and returns / GAE advantages of a window (PPO.gen_training_batch)
+hipError_t launch_rollout_record(const sl_rollout &buf, int t, const int32_t *actions, const float *probs, int n_actions,
+                                 const void *rewards, const float *values, const uint8_t *done, hipStream_t stream);
+hipError_t launch_training_batch(const sl_rollout &buf, const float *final_values, double gamma, double lmda,
+                                 float *returns, float *advantages, uint8_t *traj_start, hipStream_t stream);
 // envs [e_first, e_first + e_count) of the batch; actions / reward_t / done_t are indexed [t * tstride + e]
 // with the env's index in the whole batch
 // (sl_aql.hip dispatches the same kernel from queues of the library's own: PreparedStep below)

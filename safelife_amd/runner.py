@@ -96,6 +96,41 @@ class VectorRunner(object):
         for _ in range(n):
             yield self.take_one_step()
 
+    def gen_training_batch(self, steps_per_env, gamma=0.97, lmda=0.95):
+        """training/ppo.py:74-143 without the host: ``steps_per_env`` steps of ``take_one_step`` recorded into a
+        device-resident ``RolloutBuffer`` (one kernel per step), the policy once more on the last ``next_obs`` for the
+        open trajectories' bootstrap, and one kernel for the returns and GAE advantages, bit exact with the reference's
+        numpy arithmetic.  Returns the reference's ``obs actions action_prob returns advantages values``, flattened in
+        time-major order (``rollout.py`` says how that differs from the reference's trajectory order); the buffer, with
+        ``traj_start``, stays available as ``self.rollout`` and is overwritten by the next call."""
+        torch = self.torch
+        from .rollout import RolloutBuffer
+        T = int(steps_per_env)
+        assert T > 0
+        steps_before, copy_obs = self.num_steps, self.copy_obs
+        self.copy_obs = True        # the step overwrites the env's tensor before the row is recorded
+        try:
+            step = self.take_one_step()
+            buf = getattr(self, "rollout", None)
+            if (buf is None or buf.steps != T or buf.reward_dtype != step.rewards.dtype
+                    or buf.obs.shape[2:] != step.obs.shape[1:] or buf.obs.dtype != step.obs.dtype):
+                buf = self.rollout = RolloutBuffer(self.env.num_envs, T, tuple(step.obs.shape[1:]), step.obs.dtype,
+                                                   step.rewards.dtype, self.env.device)
+            buf.record(0, step)
+            for t in range(1, T):
+                step = self.take_one_step()
+                buf.record(t, step)
+        finally:
+            self.copy_obs = copy_obs
+        nxt = step.next_obs
+        model_in = nxt if (nxt.dtype == torch.float32 or not self.cast_obs) else nxt.to(torch.float32)
+        with torch.no_grad():
+            final_values = self.policy(model_in)[0]
+        # training/ppo.py:134 counts agent steps: steps_per_env * len(training_envs)
+        self.num_steps = steps_before + T * self.env.num_envs
+        # (envs whose last step has `done` take 0.0 instead: the kernel looks at the flag itself)
+        return buf.finish(final_values, gamma, lmda)
+
 
 class PipelinedRunner(object):
     """The same loop with the envs in GROUPS (the env's slices), each on a stream of its own: a group's observation ->
