@@ -762,6 +762,85 @@ int slhip_rollout_record(const sl_rollout *buf, int t, const int32_t *actions, c
 int slhip_training_batch(const sl_rollout *buf, const float *final_values, double gamma, double lmda, float *returns,
                          float *advantages, uint8_t *traj_start, void *stream);
 
+/* ---- DQN replay: the n-step window, the ring, sampling and the epsilon-greedy draw (additive to ABI 13: four new symbols
+ * and one new struct, nothing existing changes, so SL_ABI_VERSION stays where it is) -----------------------------------
+ * What the reference's DQN does on the host with ReplayBuffer, add_to_replay and take_one_step (training/dqn.py:21-37,
+ * 93-134), on the device.  The struct lives on the HOST; every pointer inside is a device pointer the caller owns.
+ *
+ * The window.  Every env keeps its last n = multi_step_learning steps (obs, action, float64 reward).  All envs step in
+ * lock-step, so the window is ONE ring over t mod n for all of them: slot *head is where the step being added goes, slot
+ * (*head - k) mod n holds the step k steps back, and fill[b] (0 .. n) says how many of the slots behind *head env b has
+ * filled since its last episode end.  slhip_replay_add, for the step (obs, action, r, done, next_obs) of every env b, in
+ * env order:
+ *   1. (obs0, act0, R0) = the window's slot *head -- the step n steps back -- as it is, if fill[b] == n;
+ *   2. reward of slot (*head - k) mod n += (double)r * gamma_pow[k-1] for k = 1 .. min(fill[b], n-1): a float64 product,
+ *      then a float64 add, nothing fused; slot *head = (obs, action, (double)r);
+ *   3. if fill[b] was n: push (obs0, act0, R0, obs, done) -- R0 holds n rewards;
+ *   4. if done: push (obs_k, act_k, reward_k, next_obs, done) for k = 0 .. min(fill[b] + 1, n) - 1, newest first, and
+ *      fill[b] = 0; else fill[b] = min(fill[b] + 1, n).
+ * A push writes ring slot *idx mod capacity and increments *idx.  The slots are handed out by an exclusive prefix sum of
+ * the envs' push counts (0 .. n + 1) on top of *idx, so the ring's order is the reference's whatever the device's
+ * scheduling; capacity >= B * (n + 1) makes the pushes of one call distinct slots. */
+#define SL_REPLAY_MAX_N 16        /* largest n */
+#define SL_REPLAY_MAX_K 4096      /* largest k of slhip_replay_sample */
+#define SL_REPLAY_SHORT 1         /* bit of *status: slhip_replay_sample asked for more rows than the ring holds */
+#define SL_REPLAY_BAD_INDEX 2     /* bit of *status: slhip_replay_gather met an index outside [0, capacity) and skipped it */
+typedef struct sl_replay {        /* 264 bytes */
+    long long capacity;           /* ring slots, >= B * (n + 1) */
+    long long obs_bytes;          /* bytes of one env's observation row (any dtype: rows are opaque bytes), >= 1.  Rows are
+                                   * moved 16 bytes per lane when obs_bytes and every row pointer are multiples of 16, else
+                                   * with the widest of 8 / 4 / 2 / 1 bytes that divides them all */
+    int32_t B, n;                 /* envs; window length, 1 .. SL_REPLAY_MAX_N */
+    int32_t reward_dtype;         /* SL_REWARD_F32 or SL_REWARD_F64: what slhip_replay_add's `rewards` holds */
+    int32_t reserved;
+    double gamma_pow[SL_REPLAY_MAX_N - 1];    /* gamma ** k for k = 1 .. n-1, computed by the caller (numpy's
+                                   * gamma ** np.arange(1, n) for bit parity with the reference: a device pow need not agree) */
+    uint8_t *obs;                 /* ring [capacity, obs_bytes] */
+    uint8_t *next_obs;            /* ring [capacity, obs_bytes] */
+    int32_t *action;              /* ring [capacity] */
+    double *reward;               /* ring [capacity]: the n-step sum, float64 as the reference keeps it */
+    uint8_t *done;                /* ring [capacity] 0 / 1 */
+    uint8_t *win_obs;             /* window [n, B, obs_bytes] */
+    int32_t *win_action;          /* window [n, B] */
+    double *win_reward;           /* window [n, B] */
+    int32_t *fill;                /* [B], zeroed by the caller */
+    int32_t *head;                /* one device word, zeroed by the caller: t mod n */
+    long long *idx;               /* one device int64, zeroed by the caller: pushes so far */
+    int32_t *status;              /* one device word, zeroed by the caller; the kernels only ever set bits (SL_REPLAY_*) */
+    long long *plan_base;         /* workspace [B]: the first ring slot (before the modulo) of each env's pushes */
+    int32_t *plan_code;           /* workspace [B]: fill before the step | done << 8 */
+} sl_replay;
+
+/* add_to_replay for one step of all B envs.  obs, next_obs: [B, obs_bytes]; actions: int32 [B]; rewards: [B] of
+ * buf->reward_dtype; done: uint8 [B].  next_obs of a finished env is stored as given (done = 1 masks it in the loss).
+ * Two launches on `stream`: a one-workgroup plan (counts, prefix sum, *idx, *head, fill) and one workgroup per env that
+ * updates the window and moves the rows. */
+int slhip_replay_add(const sl_replay *buf, const void *obs, const int32_t *actions, const void *rewards,
+                     const uint8_t *done, const void *next_obs, void *stream);
+
+/* k distinct indices in [0, N), N = min(*idx, capacity) read on the device, by Floyd's algorithm; 1 <= k <=
+ * SL_REPLAY_MAX_K.  For i = 0 .. k-1: j = N - k + i; z_i = the splitmix64 finalizer of seed + G * (counter * 0x100000001B3
+ * + i + 1) (G as in slhip_sample_actions); t = the high 64 bits of z_i * (j + 1); out_index[i] = t unless t is among
+ * out_index[0 .. i), else j.  The set is uniform over the k-subsets up to a bias of (j + 1) / 2^64 per draw; the order has
+ * no meaning.  k > N raises SL_REPLAY_SHORT in *status and writes nothing.  out_index: int64 [k]. */
+int slhip_replay_sample(const sl_replay *buf, int k, unsigned long long seed, unsigned long long counter,
+                        long long *out_index, void *stream);
+
+/* The five tensors of DQN.optimize for ring rows index[0 .. k): obs_out / next_obs_out [k, obs_bytes] as stored, or
+ * float32 [k, obs_bytes] widened from uint8 when obs_float32 != 0; action_out int64 [k]; reward_out float32 [k], the
+ * float64 sum rounded once; done_out float32 [k].  An index outside [0, capacity) raises SL_REPLAY_BAD_INDEX and its row
+ * is left as it was. */
+int slhip_replay_gather(const sl_replay *buf, const long long *index, int k, void *obs_out, void *next_obs_out,
+                        int obs_float32, long long *action_out, float *reward_out, float *done_out, void *stream);
+
+/* DQN.take_one_step's draw (training/dqn.py:100-104), one thread per env: z as in slhip_sample_actions from (seed,
+ * counter, e); u = (z >> 40) * 2^-24; if (double)u < epsilon the action is ((z & 0xFFFFFFFF) * n_actions) >> 32, else
+ * the first index of the row's maximum, a NaN counting as the maximum and the first NaN winning (np.argmax).
+ * epsilon <= 0 never randomises, epsilon >= 1 always does.  qvals: float32 [B, n_actions]; actions: int32 [B].  A caller
+ * that holds envs [lo, lo + B) of a larger batch passes seed + G * lo. */
+int slhip_sample_actions_eps(const float *qvals, int B, int n_actions, double epsilon, unsigned long long seed,
+                             unsigned long long counter, int32_t *actions, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

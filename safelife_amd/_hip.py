@@ -32,9 +32,12 @@ EXPORTS = (
     "slhip_queues_wait", "slhip_queues_sync", "slhip_queues_close", "slhip_queues_selftest",
     "slhip_render_boards", "slhip_env_render",
     "slhip_rollout_record", "slhip_training_batch",
+    "slhip_replay_add", "slhip_replay_sample", "slhip_replay_gather", "slhip_sample_actions_eps",
 )
 REWARD_F32, REWARD_F64 = 0, 1
 ROLLOUT_BAD_ACTION = 1
+REPLAY_MAX_N, REPLAY_MAX_K = 16, 4096
+REPLAY_SHORT, REPLAY_BAD_INDEX = 1, 2
 QUEUES_RELEASE_FREE = 1
 QUEUES_STAGE_MAX = 48
 QUEUES_SELFTEST_PLANT, QUEUES_SELFTEST_SWAP = 1, 2
@@ -151,6 +154,15 @@ class Rollout(C.Structure):
                 + [(n, C.c_void_p) for n in ("actions", "action_prob", "rewards", "values", "done", "status")])
 
 
+class Replay(C.Structure):
+    """struct sl_replay (264 bytes)"""
+    _fields_ = ([(n, C.c_longlong) for n in ("capacity", "obs_bytes")]
+                + [(n, C.c_int32) for n in ("B", "n", "reward_dtype", "reserved")]
+                + [("gamma_pow", C.c_double * (REPLAY_MAX_N - 1))]
+                + [(n, C.c_void_p) for n in ("obs", "next_obs", "action", "reward", "done", "win_obs", "win_action",
+                                             "win_reward", "fill", "head", "idx", "status", "plan_base", "plan_code")])
+
+
 class EnvBatch(C.Structure):
     _fields_ = (
         [(n, C.c_int32) for n in ENV_SCALARS_HEAD]
@@ -245,6 +257,10 @@ def lib():
         L.slhip_env_render.argtypes = [C.POINTER(EnvBatch), _p, C.c_int, C.c_int, C.c_int, _p, _p, _p]
         L.slhip_rollout_record.argtypes = [C.POINTER(Rollout), C.c_int, _p, _p, C.c_int, _p, _p, _p, _p]
         L.slhip_training_batch.argtypes = [C.POINTER(Rollout), _p, C.c_double, C.c_double, _p, _p, _p, _p]
+        L.slhip_replay_add.argtypes = [C.POINTER(Replay), _p, _p, _p, _p, _p, _p]
+        L.slhip_replay_sample.argtypes = [C.POINTER(Replay), C.c_int, C.c_ulonglong, C.c_ulonglong, _p, _p]
+        L.slhip_replay_gather.argtypes = [C.POINTER(Replay), _p, C.c_int, _p, _p, C.c_int, _p, _p, _p, _p]
+        L.slhip_sample_actions_eps.argtypes = [_p, C.c_int, C.c_int, C.c_double, C.c_ulonglong, C.c_ulonglong, _p, _p]
         L.slhip_obs_to_policy.argtypes = [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]
         L.slhip_gather_unique_id.argtypes = [_p]
         L.slhip_gather_init.argtypes = [_p, C.c_int, C.c_int, C.POINTER(_p)]

@@ -1685,6 +1685,60 @@ int slhip_training_batch(const sl_rollout *buf, const float *final_values, doubl
     return err == hipSuccess ? SL_OK : hip_fail(err, "training_batch launch");
 }
 
+static int check_replay(const sl_replay *buf) {
+    if (!buf) return fail(SL_E_ARG, "replay: null buffer description");
+    if (buf->B < 1) return fail(SL_E_ARG, "replay: B must be at least 1");
+    if (buf->n < 1 || buf->n > SL_REPLAY_MAX_N) return fail(SL_E_ARG, "replay: n outside 1..SL_REPLAY_MAX_N");
+    if (buf->obs_bytes < 1) return fail(SL_E_ARG, "replay: obs_bytes must be at least 1");
+    if (buf->capacity < (long long)buf->B * (buf->n + 1))
+        return fail(SL_E_ARG, "replay: capacity smaller than B * (n + 1)");
+    if (buf->reward_dtype != SL_REWARD_F32 && buf->reward_dtype != SL_REWARD_F64)
+        return fail(SL_E_ARG, "replay: reward_dtype must be SL_REWARD_F32 or SL_REWARD_F64");
+    if (!buf->obs || !buf->next_obs || !buf->action || !buf->reward || !buf->done || !buf->idx || !buf->status)
+        return fail(SL_E_ARG, "replay: null ring pointer");
+    return SL_OK;
+}
+
+int slhip_replay_add(const sl_replay *buf, const void *obs, const int32_t *actions, const void *rewards,
+                     const uint8_t *done, const void *next_obs, void *stream) {
+    if (int rc = check_replay(buf)) return rc;
+    if (!buf->win_obs || !buf->win_action || !buf->win_reward || !buf->fill || !buf->head || !buf->plan_base || !buf->plan_code)
+        return fail(SL_E_ARG, "replay_add: null window / workspace pointer");
+    if (!obs || !actions || !rewards || !done || !next_obs) return fail(SL_E_ARG, "replay_add: null pointer");
+    const hipError_t err = sl::launch_replay_add(*buf, obs, actions, rewards, done, next_obs, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "replay_add launch");
+}
+
+int slhip_replay_sample(const sl_replay *buf, int k, unsigned long long seed, unsigned long long counter,
+                        long long *out_index, void *stream) {
+    if (int rc = check_replay(buf)) return rc;
+    if (k < 1 || k > SL_REPLAY_MAX_K) return fail(SL_E_ARG, "replay_sample: k outside 1..SL_REPLAY_MAX_K");
+    if (!out_index) return fail(SL_E_ARG, "replay_sample: null pointer");
+    const hipError_t err = sl::launch_replay_sample(*buf, k, seed, counter, out_index, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "replay_sample launch");
+}
+
+int slhip_replay_gather(const sl_replay *buf, const long long *index, int k, void *obs_out, void *next_obs_out,
+                        int obs_float32, long long *action_out, float *reward_out, float *done_out, void *stream) {
+    if (int rc = check_replay(buf)) return rc;
+    if (k < 1) return fail(SL_E_ARG, "replay_gather: k must be at least 1");
+    if (!index || !obs_out || !next_obs_out || !action_out || !reward_out || !done_out)
+        return fail(SL_E_ARG, "replay_gather: null pointer");
+    const hipError_t err = sl::launch_replay_gather(*buf, index, k, obs_out, next_obs_out, obs_float32, action_out, reward_out,
+                                                    done_out, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "replay_gather launch");
+}
+
+int slhip_sample_actions_eps(const float *qvals, int B, int n_actions, double epsilon, unsigned long long seed,
+                             unsigned long long counter, int32_t *actions, void *stream) {
+    if (B < 0 || n_actions < 1) return fail(SL_E_ARG, "sample_actions_eps: B must be >= 0 and n_actions >= 1");
+    if (!(epsilon == epsilon)) return fail(SL_E_ARG, "sample_actions_eps: epsilon is NaN");
+    if (B == 0) return SL_OK;
+    if (!qvals || !actions) return fail(SL_E_ARG, "sample_actions_eps: null pointer");
+    const hipError_t err = sl::launch_sample_actions_eps(qvals, B, n_actions, epsilon, seed, counter, actions, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "sample_actions_eps launch");
+}
+
 int slhip_obs_to_policy(const uint32_t *view, int B, int vh, int vw, const int32_t *channels, int C, void *out,
                         int dtype, void *stream) {
     if (B < 0 || vh < 1 || vw < 1) return fail(SL_E_ARG, "bad view shape");

@@ -19,6 +19,7 @@ instead of ``(id(env), env.num_resets, k)``), so trajectories are strung togethe
 import collections
 
 StepResult = collections.namedtuple("StepResult", "obs actions rewards done next_obs agent_ids policies values")
+DQNStep = collections.namedtuple("DQNStep", "obs actions rewards done next_obs agent_ids")
 
 _SPLITMIX_G = 0x9E3779B97F4A7C15        # the increment of the draw kernel's splitmix64 (slhip_sample_actions)
 
@@ -130,6 +131,80 @@ class VectorRunner(object):
         self.num_steps = steps_before + T * self.env.num_envs
         # (envs whose last step has `done` take 0.0 instead: the kernel looks at the flag itself)
         return buf.finish(final_values, gamma, lmda)
+
+
+class DQNRunner(object):
+    """The driver loop of the reference's DQN (training/dqn.py:93-108, 177-191) without the host: Q-values from the
+    model, the epsilon-greedy draw on the device (``slhip_sample_actions_eps``: ``argmax`` taking the first maximum, or a
+    uniform action with probability epsilon, straight into the int32 tensor the step kernel reads), the fused step, and
+    ``collect`` feeding every step to a ``replay.ReplayBuffer``.  The action of env e at step c is a function of
+    ``(seed, c, env.env_offset + e)``, its Q-values and epsilon alone.
+
+    Parameters: `env` as for ``VectorRunner`` (``policy_layout=...``, ``auto_reset=True``);
+    ``q_model(obs [B,C,W,H]) -> qvals [B,A]`` on the device; ``cast_obs``: True hands the model float32 (dqn.py:97),
+    False the env's tensor as it is.
+    """
+
+    def __init__(self, env, q_model, seed=0, cast_obs=True):
+        import torch
+        from . import _hip
+        self.torch, self._hip = torch, _hip
+        if env.policy_tensor is None:
+            raise ValueError("DQNRunner needs SafeLifeVectorEnv(policy_layout=...)")
+        if not env.auto_reset:
+            raise ValueError("DQNRunner needs auto_reset=True (finished envs reload inside the step kernel)")
+        self.env, self.q_model, self.cast_obs = env, q_model, cast_obs
+        B = env.num_envs
+        self.seed = (int(seed) + _SPLITMIX_G * int(env.env_offset)) & (2 ** 64 - 1)
+        self.env_ids = torch.arange(B, device=env.device, dtype=torch.int64)
+        self.num_resets = torch.zeros(B, device=env.device, dtype=torch.int64)
+        self.actions = torch.zeros(B, dtype=torch.int32, device=env.device)
+        self.num_steps = 0          # agent steps, as dqn.py:191 counts them
+        self.draws = 0              # the draw counter: steps taken
+        self._started = False
+        self._lib = _hip.lib()
+
+    def take_one_step(self, epsilon):
+        """``obs actions rewards done next_obs agent_ids`` of one step of every env: ``obs`` is an own copy (the step
+        overwrites the env's tensor), ``actions`` an own int32 copy, ``rewards`` the wrapped float64 reward when the env
+        has ``wrappers=``, the game's float32 reward otherwise; ``next_obs`` is the env's tensor -- valid until the next
+        step, and for a finished env already the first observation of its next episode."""
+        torch, env, _hip = self.torch, self.env, self._hip
+        if not self._started:
+            env.reset()
+            self._started = True
+        obs = env.policy_tensor
+        agent_ids = (self.env_ids, self.num_resets.clone())
+        model_in = obs if (obs.dtype == torch.float32 or not self.cast_obs) else obs.to(torch.float32)
+        with torch.no_grad():
+            qvals = self.q_model(model_in)
+        if qvals.dtype != torch.float32 or not qvals.is_contiguous():
+            qvals = qvals.to(torch.float32).contiguous()
+        if qvals.dim() != 2 or qvals.shape[0] != env.num_envs:
+            raise ValueError("q_model must return [num_envs, n_actions]")
+        rc = self._lib.slhip_sample_actions_eps(_hip.ptr(qvals), env.num_envs, qvals.shape[1], float(epsilon), self.seed,
+                                                self.draws, _hip.ptr(self.actions), _hip.current_stream_ptr())
+        if rc:
+            _hip.check(rc)
+        self.draws += 1
+        kept = obs.clone()
+        env.step(self.actions)
+        shaped = getattr(env, "shaped_reward", None)
+        rewards = shaped.clone() if shaped is not None else env.reward.clone()
+        done = env.done.to(torch.bool)
+        self.num_resets += done.to(torch.int64)
+        return DQNStep(kept, self.actions.clone(), rewards, done, env.policy_tensor, agent_ids)
+
+    def collect(self, steps, epsilon, replay):
+        """``steps`` steps of every env, each added to ``replay`` (``add_to_replay``); ``epsilon`` is a number or a
+        function of ``num_steps`` (the reference's ``epsilon_schedule``).  Returns the last step."""
+        step = None
+        for _ in range(int(steps)):
+            eps = epsilon(self.num_steps) if callable(epsilon) else epsilon
+            step = self.take_one_step(float(eps))
+            replay.add(step)
+            self.num_steps += self.env.num_envs
+        return step
 
 
 class PipelinedRunner(object):
