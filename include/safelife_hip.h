@@ -841,6 +841,75 @@ int slhip_replay_gather(const sl_replay *buf, const long long *index, int k, voi
 int slhip_sample_actions_eps(const float *qvals, int B, int n_actions, double epsilon, unsigned long long seed,
                              unsigned long long counter, int32_t *actions, void *stream);
 
+/* ---- multi-agent PPO training batches: the masked rollout window (additive to ABI 13: seven new symbols and one new
+ * struct, nothing existing changes, so SL_ABI_VERSION stays where it is) ------------------------------------------------
+ * The reference's driver loop for envs with several agents (training/base_algo.py:152-244 with ppo.py:74-143): the agents
+ * of one env finish at different steps, a finished agent gets no observation row and no action (the env is handed 0 for
+ * it), the env resets once ALL its agents are done, and a trajectory is the steps of one (env, reset count, agent).
+ * Here the window is [T, B] with B = envs * n_agents COLUMNS, column e * n_agents + a being agent a of env e, plus
+ * active [T, B]: 1 where the agent took part in step t.  The rules, per column:
+ *   - a trajectory is a run of contiguous active rows; it ends at a row with done != 0 (CLOSED, final_value 0.0) or at the
+ *     window's last row (OPEN, final_value = final_values[column]).  Inactive rows only ever sit between a done row and
+ *     the next trajectory's first row, or at the head of the window (an agent that was gone when the window began);
+ *   - a row starts a trajectory when it is active and t == 0, or the row before it is inactive or has done != 0;
+ *   - a column whose last row is inactive or done takes no bootstrap: its final_values entry is not used;
+ *   - width, returns and advantages of a trajectory are those of slhip_training_batch, float64 islands included.
+ * The carried state between steps -- and between windows -- is active_now [B] (the reference's ~last_done) and
+ * num_resets [envs]: after a step, active_now &= ~done; an env with no agent left has been reloaded by the step kernel
+ * (auto_reset), so all its agents become active again and its num_resets goes up by one. */
+#define SL_ROLLOUT_BAD_INDEX 2    /* bit of *status: slhip_rollout_gather met a row id outside [0, T * B) and skipped it */
+#define SL_ROLLOUT_SCAN_CHUNK 4096 /* flags per workgroup of slhip_rollout_compact: its workspace holds one int32 per chunk */
+typedef struct sl_rollout_multi { /* 96 bytes */
+    sl_rollout w;                 /* the window; w.B = envs * n_agents columns */
+    int32_t n_agents;             /* agents per env, 1 .. 8; w.B is a multiple of it */
+    int32_t reserved;
+    uint8_t *active;              /* [T, w.row_stride] 0 / 1 */
+} sl_rollout_multi;
+
+/* slhip_sample_actions with a mask: rows with active[e] == 0 get action 0 whatever their probabilities hold (NaN rows
+ * included: they are not read); every other row gets exactly the draw of slhip_sample_actions for row e.  active: uint8
+ * [B] (NULL: all active).  For a multi-agent batch the rows are the columns e * n_agents + a, and a caller that holds
+ * envs [lo, hi) of a larger run passes seed + G * lo * n_agents. */
+int slhip_sample_actions_masked(const float *probs, const uint8_t *active, int B, int n_actions, unsigned long long seed,
+                                unsigned long long counter, int32_t *actions, void *stream);
+
+/* Step t of the window, and the carried state moved on, in one launch.  Row t takes what slhip_rollout_record takes for
+ * the columns with active_now != 0, and active[t] = active_now; an inactive column records action 0, probability 0,
+ * reward 0, value 0 and done 0, and none of its inputs is looked at (no SL_ROLLOUT_BAD_ACTION either).  Then, per env:
+ * active_now &= ~done; if no agent is left, active_now = 1 for all of them and num_resets[env] += 1.
+ * actions int32, rewards (buf->w.reward_dtype), values float32, done uint8, active_now uint8: [B]; probs float32
+ * [B, n_actions]; num_resets int64 [B / n_agents]. */
+int slhip_rollout_record_multi(const sl_rollout_multi *buf, int t, const int32_t *actions, const float *probs,
+                               int n_actions, const void *rewards, const float *values, const uint8_t *done,
+                               uint8_t *active_now, long long *num_resets, void *stream);
+
+/* Returns and advantages of the window by the rules above; arguments as slhip_training_batch.  Outputs at inactive rows
+ * are left as they are (traj_start included).  With n_agents == 1 and every row active the outputs equal
+ * slhip_training_batch's bit for bit. */
+int slhip_training_batch_multi(const sl_rollout_multi *buf, const float *final_values, double gamma, double lmda,
+                               float *returns, float *advantages, uint8_t *traj_start, void *stream);
+
+/* The dense row ids t * B + column of the active rows, ascending -- (t, env, agent) order -- and their number: an exclusive
+ * prefix sum of the flags over the whole window.  Two launches: every workgroup counts its chunk of SL_ROLLOUT_SCAN_CHUNK
+ * flags into workspace[chunk]; then every workgroup sums the counts in front of its chunk, scans the chunk again (from
+ * L2) and writes.  A row's place is a function of the flags alone: no atomic and no arrival order takes part.
+ * rows_out: int64 [T * B], entries [0, N) are written; count_out: int64 [1] = N; workspace: int32
+ * [slhip_rollout_compact_chunks(buf)]. */
+int slhip_rollout_compact_chunks(const sl_rollout_multi *buf);
+int slhip_rollout_compact(const sl_rollout_multi *buf, long long *rows_out, long long *count_out, int32_t *workspace,
+                          void *stream);
+
+/* The reference's flat tensors for rows[0 .. n): row id i = t * B + c reads element t * w.row_stride + c of the window's
+ * arrays and t * w.out_stride + c of returns / advantages.  actions_out int64 [n]; action_prob_out, returns_out,
+ * advantages_out, values_out float32 [n].  obs (optional, NULL: skipped): [T * B, obs_bytes] dense, rows are opaque bytes,
+ * moved to obs_out [n, obs_bytes] 16 bytes per lane when obs_bytes and both pointers are multiples of 16, else with the
+ * widest of 8 / 4 / 2 / 1 bytes that divides them all.  A row id outside [0, T * B) raises SL_ROLLOUT_BAD_INDEX in
+ * *w.status and its output row is left as it was; nothing is read through it. */
+int slhip_rollout_gather(const sl_rollout_multi *buf, const long long *rows, long long n, const float *returns,
+                         const float *advantages, const void *obs, long long obs_bytes, void *obs_out,
+                         long long *actions_out, float *action_prob_out, float *returns_out, float *advantages_out,
+                         float *values_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,9 +33,12 @@ EXPORTS = (
     "slhip_render_boards", "slhip_env_render",
     "slhip_rollout_record", "slhip_training_batch",
     "slhip_replay_add", "slhip_replay_sample", "slhip_replay_gather", "slhip_sample_actions_eps",
+    "slhip_sample_actions_masked", "slhip_rollout_record_multi", "slhip_training_batch_multi",
+    "slhip_rollout_compact_chunks", "slhip_rollout_compact", "slhip_rollout_gather",
 )
 REWARD_F32, REWARD_F64 = 0, 1
-ROLLOUT_BAD_ACTION = 1
+ROLLOUT_BAD_ACTION, ROLLOUT_BAD_INDEX = 1, 2
+ROLLOUT_SCAN_CHUNK = 4096
 REPLAY_MAX_N, REPLAY_MAX_K = 16, 4096
 REPLAY_SHORT, REPLAY_BAD_INDEX = 1, 2
 QUEUES_RELEASE_FREE = 1
@@ -154,6 +157,11 @@ class Rollout(C.Structure):
                 + [(n, C.c_void_p) for n in ("actions", "action_prob", "rewards", "values", "done", "status")])
 
 
+class RolloutMulti(C.Structure):
+    """struct sl_rollout_multi (96 bytes)"""
+    _fields_ = [("w", Rollout), ("n_agents", C.c_int32), ("reserved", C.c_int32), ("active", C.c_void_p)]
+
+
 class Replay(C.Structure):
     """struct sl_replay (264 bytes)"""
     _fields_ = ([(n, C.c_longlong) for n in ("capacity", "obs_bytes")]
@@ -261,6 +269,13 @@ def lib():
         L.slhip_replay_sample.argtypes = [C.POINTER(Replay), C.c_int, C.c_ulonglong, C.c_ulonglong, _p, _p]
         L.slhip_replay_gather.argtypes = [C.POINTER(Replay), _p, C.c_int, _p, _p, C.c_int, _p, _p, _p, _p]
         L.slhip_sample_actions_eps.argtypes = [_p, C.c_int, C.c_int, C.c_double, C.c_ulonglong, C.c_ulonglong, _p, _p]
+        L.slhip_sample_actions_masked.argtypes = [_p, _p, C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, _p, _p]
+        L.slhip_rollout_record_multi.argtypes = [C.POINTER(RolloutMulti), C.c_int, _p, _p, C.c_int, _p, _p, _p, _p, _p, _p]
+        L.slhip_training_batch_multi.argtypes = [C.POINTER(RolloutMulti), _p, C.c_double, C.c_double, _p, _p, _p, _p]
+        L.slhip_rollout_compact_chunks.argtypes = [C.POINTER(RolloutMulti)]
+        L.slhip_rollout_compact.argtypes = [C.POINTER(RolloutMulti), _p, _p, _p, _p]
+        L.slhip_rollout_gather.argtypes = [C.POINTER(RolloutMulti), _p, C.c_longlong, _p, _p, _p, C.c_longlong, _p,
+                                           _p, _p, _p, _p, _p, _p]
         L.slhip_obs_to_policy.argtypes = [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]
         L.slhip_gather_unique_id.argtypes = [_p]
         L.slhip_gather_init.argtypes = [_p, C.c_int, C.c_int, C.POINTER(_p)]

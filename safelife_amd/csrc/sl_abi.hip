@@ -1685,6 +1685,81 @@ int slhip_training_batch(const sl_rollout *buf, const float *final_values, doubl
     return err == hipSuccess ? SL_OK : hip_fail(err, "training_batch launch");
 }
 
+static int check_rollout_multi(const sl_rollout_multi *buf) {
+    if (!buf) return fail(SL_E_ARG, "rollout_multi: null buffer description");
+    if (int rc = check_rollout(&buf->w)) return rc;
+    if (buf->n_agents < 1 || buf->n_agents > 8 || buf->w.B % buf->n_agents)
+        return fail(SL_E_ARG, "rollout_multi: n_agents outside 1..8 or B not a multiple of it");
+    if (!buf->active) return fail(SL_E_ARG, "rollout_multi: null active");
+    return SL_OK;
+}
+
+int slhip_sample_actions_masked(const float *probs, const uint8_t *active, int B, int n_actions, unsigned long long seed,
+                                unsigned long long counter, int32_t *actions, void *stream) {
+    if (B < 0 || n_actions < 1 || n_actions > 64) return fail(SL_E_ARG, "sample_actions_masked: bad sizes");
+    if (!probs || !actions) return fail(SL_E_ARG, "sample_actions_masked: null pointer");
+    if (B == 0) return SL_OK;
+    const hipError_t err = sl::launch_sample_actions_masked(probs, active, B, n_actions, seed, counter, actions, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "sample_actions_masked launch");
+}
+
+int slhip_rollout_record_multi(const sl_rollout_multi *buf, int t, const int32_t *actions, const float *probs,
+                               int n_actions, const void *rewards, const float *values, const uint8_t *done,
+                               uint8_t *active_now, long long *num_resets, void *stream) {
+    if (int rc = check_rollout_multi(buf)) return rc;
+    if (!buf->w.actions || !buf->w.action_prob || !buf->w.status)
+        return fail(SL_E_ARG, "rollout_multi: null actions / action_prob / status");
+    if (t < 0 || t >= buf->w.T) return fail(SL_E_ARG, "rollout_record_multi: t outside [0, T)");
+    if (n_actions < 1) return fail(SL_E_ARG, "rollout_record_multi: n_actions must be at least 1");
+    if (!actions || !probs || !rewards || !values || !done || !active_now || !num_resets)
+        return fail(SL_E_ARG, "rollout_record_multi: null pointer");
+    const hipError_t err = sl::launch_rollout_record_multi(*buf, t, actions, probs, n_actions, rewards, values, done,
+                                                           active_now, num_resets, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "rollout_record_multi launch");
+}
+
+int slhip_training_batch_multi(const sl_rollout_multi *buf, const float *final_values, double gamma, double lmda,
+                               float *returns, float *advantages, uint8_t *traj_start, void *stream) {
+    if (int rc = check_rollout_multi(buf)) return rc;
+    if (buf->w.out_stride < buf->w.B) return fail(SL_E_ARG, "training_batch_multi: out_stride smaller than B");
+    if (!final_values || !returns || !advantages) return fail(SL_E_ARG, "training_batch_multi: null pointer");
+    const hipError_t err = sl::launch_training_batch_multi(*buf, final_values, gamma, lmda, returns, advantages, traj_start,
+                                                           (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "training_batch_multi launch");
+}
+
+int slhip_rollout_compact_chunks(const sl_rollout_multi *buf) {
+    if (check_rollout_multi(buf)) return 0;
+    return sl::rollout_compact_chunks(*buf);
+}
+
+int slhip_rollout_compact(const sl_rollout_multi *buf, long long *rows_out, long long *count_out, int32_t *workspace,
+                          void *stream) {
+    if (int rc = check_rollout_multi(buf)) return rc;
+    if (!rows_out || !count_out || !workspace) return fail(SL_E_ARG, "rollout_compact: null pointer");
+    const hipError_t err = sl::launch_rollout_compact(*buf, rows_out, count_out, workspace, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "rollout_compact launch");
+}
+
+int slhip_rollout_gather(const sl_rollout_multi *buf, const long long *rows, long long n, const float *returns,
+                         const float *advantages, const void *obs, long long obs_bytes, void *obs_out,
+                         long long *actions_out, float *action_prob_out, float *returns_out, float *advantages_out,
+                         float *values_out, void *stream) {
+    if (int rc = check_rollout_multi(buf)) return rc;
+    if (!buf->w.actions || !buf->w.action_prob || !buf->w.status)
+        return fail(SL_E_ARG, "rollout_multi: null actions / action_prob / status");
+    if (buf->w.out_stride < buf->w.B) return fail(SL_E_ARG, "rollout_gather: out_stride smaller than B");
+    if (n < 0 || n > (long long)buf->w.T * buf->w.B) return fail(SL_E_ARG, "rollout_gather: n outside [0, T * B]");
+    if (obs && (obs_bytes < 1 || !obs_out)) return fail(SL_E_ARG, "rollout_gather: obs needs obs_bytes >= 1 and obs_out");
+    if (n == 0) return SL_OK;
+    if (!rows || !returns || !advantages || !actions_out || !action_prob_out || !returns_out || !advantages_out || !values_out)
+        return fail(SL_E_ARG, "rollout_gather: null pointer");
+    const hipError_t err = sl::launch_rollout_gather(*buf, rows, n, returns, advantages, obs, obs_bytes, obs_out, actions_out,
+                                                     action_prob_out, returns_out, advantages_out, values_out,
+                                                     (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "rollout_gather launch");
+}
+
 static int check_replay(const sl_replay *buf) {
     if (!buf) return fail(SL_E_ARG, "replay: null buffer description");
     if (buf->B < 1) return fail(SL_E_ARG, "replay: B must be at least 1");

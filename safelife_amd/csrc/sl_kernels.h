@@ -86,6 +86,21 @@ hipError_t launch_rollout_record(const sl_rollout &buf, int t, const int32_t *ac
                                  const void *rewards, const float *values, const uint8_t *done, hipStream_t stream);
 hipError_t launch_training_batch(const sl_rollout &buf, const float *final_values, double gamma, double lmda,
                                  float *returns, float *advantages, uint8_t *traj_start, hipStream_t stream);
+// sl_rollout_multi.hip : the masked window of multi-agent envs -- masked draw, record, returns / GAE, compaction, gather
+hipError_t launch_sample_actions_masked(const float *probs, const uint8_t *active, int B, int A, unsigned long long seed,
+                                        unsigned long long counter, int32_t *actions, hipStream_t stream);
+hipError_t launch_rollout_record_multi(const sl_rollout_multi &buf, int t, const int32_t *actions, const float *probs,
+                                       int n_actions, const void *rewards, const float *values, const uint8_t *done,
+                                       uint8_t *active_now, long long *num_resets, hipStream_t stream);
+hipError_t launch_training_batch_multi(const sl_rollout_multi &buf, const float *final_values, double gamma, double lmda,
+                                       float *returns, float *advantages, uint8_t *traj_start, hipStream_t stream);
+int rollout_compact_chunks(const sl_rollout_multi &buf);
+hipError_t launch_rollout_compact(const sl_rollout_multi &buf, long long *rows_out, long long *count_out, int32_t *workspace,
+                                  hipStream_t stream);
+hipError_t launch_rollout_gather(const sl_rollout_multi &buf, const long long *rows, long long n, const float *returns,
+                                 const float *advantages, const void *obs, long long obs_bytes, void *obs_out,
+                                 long long *actions_out, float *action_prob_out, float *returns_out, float *advantages_out,
+                                 float *values_out, hipStream_t stream);
 // sl_replay.hip : DQN's n-step window and replay ring, its sampler and gather, the epsilon-greedy draw
 hipError_t launch_replay_add(const sl_replay &buf, const void *obs, const int32_t *actions, const void *rewards,
                              const uint8_t *done, const void *next_obs, hipStream_t stream);

@@ -9,7 +9,8 @@ last observation (training/base_algo.py:152-244, training/ppo.py:61-73).  Here t
 convolves (``policy_layout``), actions are sampled on the device, finished envs are reloaded inside the step
 kernel (``auto_reset``), and nothing visits the host.
 
-What carries over from the reference, per step and per agent (= per env: the fused path is single-agent):
+What carries over from the reference, per step and per agent (= per env for ``VectorRunner``, ``DQNRunner`` and
+``PipelinedRunner``; ``MultiAgentRunner`` at the end of the file drives envs with several agents):
 ``obs, actions, rewards, done, next_obs, agent_ids, policies, values`` with the reference's meaning --
 ``done`` describes the step that was just taken, ``next_obs`` of a finished env is already the first
 observation of its next episode, and an agent id changes when its env resets (``(env index, resets so far)``
@@ -20,6 +21,7 @@ import collections
 
 StepResult = collections.namedtuple("StepResult", "obs actions rewards done next_obs agent_ids policies values")
 DQNStep = collections.namedtuple("DQNStep", "obs actions rewards done next_obs agent_ids")
+MultiAgentStep = collections.namedtuple("MultiAgentStep", StepResult._fields + ("active",))
 
 _SPLITMIX_G = 0x9E3779B97F4A7C15        # the increment of the draw kernel's splitmix64 (slhip_sample_actions)
 
@@ -302,3 +304,137 @@ class PipelinedRunner(object):
     def finish(self):
         """The caller's current stream waits for every group."""
         self.env.join()
+
+
+class MultiAgentRunner(object):
+    """The driver loop of the reference's trainers for envs with SEVERAL agents (training/base_algo.py:152-244 with
+    training/ppo.py:61-143), without the host.  The agents of one env finish at different steps; a finished agent gets no
+    action (the env is handed 0 for it) and no row in the training batch until its env reloads, which happens -- inside the
+    step kernel -- once ALL its agents are done.  Who is active is kept on the device (``active`` uint8 ``[B, A]``, the
+    reference's ``~last_done``; ``num_resets`` int64 ``[B]``) and carried from step to step and from one
+    ``gen_training_batch`` to the next.
+
+    The reference hands its model the active agents' observations only.  Here the policy is called on ALL ``B * A`` rows
+    and what it returns for inactive rows is ignored (their action is 0 whatever the probabilities hold, NaN included):
+    a compacted input would need the active count on the host every step.  The action of agent ``a`` of env ``e`` at step
+    ``c`` is the draw of ``slhip_sample_actions`` for row ``(env_offset + e) * A + a`` under ``(seed, c)``.
+
+    Parameters: ``env`` a ``SafeLifeMultiAgentVectorEnv(policy_layout=..., auto_reset=True)``;
+    ``policy(obs [B*A, C, vw, vh]) -> (values [B*A], probs float32 [B*A, n_actions])`` on the device; ``cast_obs``: True
+    hands the model float32 (training/ppo.py:64), False the env's tensor as it is.
+    """
+
+    def __init__(self, env, policy, seed=0, cast_obs=True):
+        import torch
+        from . import _hip
+        from .rollout import MultiAgentRolloutBuffer
+        self.torch, self._hip, self._buffer = torch, _hip, MultiAgentRolloutBuffer
+        if getattr(env, "n_agents", None) is None or env.policy_tensor is None:
+            raise ValueError("MultiAgentRunner needs SafeLifeMultiAgentVectorEnv(policy_layout=...)")
+        if not env.base.auto_reset:
+            raise ValueError("MultiAgentRunner needs auto_reset=True (an env reloads inside the step kernel once all its "
+                             "agents are done)")
+        self.env, self.policy, self.cast_obs = env, policy, cast_obs
+        B, A = env.num_envs, env.n_agents
+        self.seed = (int(seed) + _SPLITMIX_G * int(env.base.env_offset) * A) & (2 ** 64 - 1)
+        self.env_ids = torch.arange(B, device=env.device, dtype=torch.int64)
+        self.actions = torch.zeros((B, A), dtype=torch.int32, device=env.device)
+        #: agent steps taken so far -- what ppo.py:134 would count with per-agent lists -- as a device tensor
+        self.num_agent_steps = torch.zeros(1, dtype=torch.int64, device=env.device)
+        self.num_steps = 0          # env steps * envs, as ppo.py:134 counts
+        self.draws = 0              # the draw counter: steps taken
+        self.rollout = None
+        # the carried state lives in a one-step buffer until gen_training_batch makes the real one
+        self._state = MultiAgentRolloutBuffer(B, A, 1, None, None, self._reward_dtype(), env.device)
+        self._started = False
+        self._lib = _hip.lib()
+
+    def _reward_dtype(self):
+        env = self.env
+        return (env.shaped_reward if env.shaped_reward is not None else env.reward).dtype
+
+    @property
+    def active(self):
+        """uint8 [B, A]: who takes part in the NEXT step."""
+        return self._state.active_now
+
+    @property
+    def num_resets(self):
+        """int64 [B]: reloads of every env so far (``env.num_resets`` of the reference)."""
+        return self._state.num_resets
+
+    def _model_in(self, obs):
+        torch = self.torch
+        x = obs.view((-1,) + tuple(obs.shape[2:]))
+        return x if (x.dtype == torch.float32 or not self.cast_obs) else x.to(torch.float32)
+
+    def _step(self):
+        """Model, masked draw, fused step -- everything but the bookkeeping, which ``record_multi`` does."""
+        torch, env, _hip = self.torch, self.env, self._hip
+        if not self._started:
+            env.reset()
+            self._started = True
+        B, A = env.num_envs, env.n_agents
+        obs = env.policy_tensor
+        with torch.no_grad():
+            values, policies = self.policy(self._model_in(obs))
+        if policies.dtype != torch.float32 or not policies.is_contiguous():
+            policies = policies.to(torch.float32).contiguous()
+        if policies.dim() != 2 or policies.shape[0] != B * A:
+            raise ValueError("policy must return probabilities [num_envs * n_agents, n_actions]")
+        state = self._state
+        active = state.active_now.clone()
+        agent_ids = (self.env_ids, state.num_resets.clone())
+        rc = self._lib.slhip_sample_actions_masked(_hip.ptr(policies), _hip.ptr(active), B * A, policies.shape[1],
+                                                   self.seed, self.draws, _hip.ptr(self.actions),
+                                                   _hip.current_stream_ptr())
+        if rc:
+            _hip.check(rc)
+        self.draws += 1
+        kept = obs.clone()
+        env.step(self.actions)
+        rewards = (env.shaped_reward if env.shaped_reward is not None else env.reward).clone()
+        done = env.done.to(torch.bool)
+        self.num_agent_steps += active.sum()
+        self.num_steps += B
+        return MultiAgentStep(kept, self.actions.clone(), rewards, done, env.policy_tensor, agent_ids,
+                              policies.view(B, A, -1), values.reshape(B, A), active)
+
+    def take_one_step(self):
+        """One step of every env: the ``StepResult`` fields shaped ``[B, A, ...]`` plus ``active`` uint8 ``[B, A]`` -- who
+        took part; the rows of the others are to be ignored (their action is 0).  ``agent_ids`` is ``(env index [B],
+        resets so far [B])``, the agent being the column.  ``rewards`` is ``env.shaped_reward`` when the env has
+        ``wrappers=``, else ``env.reward``; ``next_obs`` is the env's tensor, valid until the next step.  (The bookkeeping
+        runs through row 0 of the buffer that holds the carried state -- after a ``gen_training_batch`` that is
+        ``self.rollout``, whose window is then no longer whole.)"""
+        step = self._step()
+        self._state.record(0, step)         # moves active / num_resets on (the one-step window itself is not used)
+        return step
+
+    def gen_training_batch(self, steps_per_env, gamma=0.97, lmda=0.95, gather_obs=True, dense=False):
+        """training/ppo.py:74-143 for multi-agent envs without the host loop: ``steps_per_env`` steps recorded into a
+        ``MultiAgentRolloutBuffer`` (``self.rollout``: ``rows``, ``agent_ids``, ``traj_start``, ``active``), the policy
+        once more on the last ``next_obs`` for the bootstrap of the agents that go on, one kernel for returns and
+        advantages, and the active rows gathered in ``(t, b, a)`` order -- bit exact with the reference's numpy
+        arithmetic.  One host visit per window (the row count; none with ``dense=True``).  ``active`` and ``num_resets``
+        persist: the next window starts with whoever is gone now."""
+        torch, env = self.torch, self.env
+        T = int(steps_per_env)
+        assert T > 0
+        step = self._step()
+        buf = self.rollout
+        if (buf is None or buf.steps != T or buf.reward_dtype != step.rewards.dtype
+                or buf.obs.shape[2:] != step.obs.shape[2:] or buf.obs.dtype != step.obs.dtype):
+            buf = self.rollout = self._buffer(env.num_envs, env.n_agents, T, tuple(step.obs.shape[2:]), step.obs.dtype,
+                                              step.rewards.dtype, env.device)
+        if buf is not self._state:           # the carried state moves into the window's buffer
+            buf.active_now.copy_(self._state.active_now)
+            buf.num_resets.copy_(self._state.num_resets)
+            self._state = buf
+        buf.record(0, step)
+        for t in range(1, T):
+            step = self._step()
+            buf.record(t, step)
+        with torch.no_grad():
+            final_values = self.policy(self._model_in(step.next_obs))[0]
+        return buf.finish(final_values.reshape(env.num_envs, env.n_agents), gamma, lmda, gather_obs=gather_obs, dense=dense)
