@@ -1650,7 +1650,7 @@ int slhip_sample_actions(const float *probs, int B, int n_actions, unsigned long
     if (B < 0 || n_actions < 1 || n_actions > 64) return fail(SL_E_ARG, "bad sizes");
     if (!probs || !actions) return fail(SL_E_ARG, "null pointer");
     if (B == 0) return SL_OK;
-    hipError_t err = sl::launch_sample_actions(probs, B, n_actions, seed, counter, actions, (hipStream_t)stream);
+    hipError_t err = sl::launch_sample_actions(probs, nullptr, B, n_actions, seed, counter, actions, (hipStream_t)stream);
     return err == hipSuccess ? SL_OK : hip_fail(err, "sample_actions launch");
 }
 
@@ -1680,8 +1680,8 @@ int slhip_training_batch(const sl_rollout *buf, const float *final_values, doubl
     if (int rc = check_rollout(buf)) return rc;
     if (buf->out_stride < buf->B) return fail(SL_E_ARG, "training_batch: out_stride smaller than B");
     if (!final_values || !returns || !advantages) return fail(SL_E_ARG, "training_batch: null pointer");
-    const hipError_t err = sl::launch_training_batch(*buf, final_values, gamma, lmda, returns, advantages, traj_start,
-                                                     (hipStream_t)stream);
+    const hipError_t err = sl::launch_training_batch(*buf, nullptr, final_values, gamma, lmda, returns, advantages,
+                                                     traj_start, (hipStream_t)stream);
     return err == hipSuccess ? SL_OK : hip_fail(err, "training_batch launch");
 }
 
@@ -1699,7 +1699,7 @@ int slhip_sample_actions_masked(const float *probs, const uint8_t *active, int B
     if (B < 0 || n_actions < 1 || n_actions > 64) return fail(SL_E_ARG, "sample_actions_masked: bad sizes");
     if (!probs || !actions) return fail(SL_E_ARG, "sample_actions_masked: null pointer");
     if (B == 0) return SL_OK;
-    const hipError_t err = sl::launch_sample_actions_masked(probs, active, B, n_actions, seed, counter, actions, (hipStream_t)stream);
+    const hipError_t err = sl::launch_sample_actions(probs, active, B, n_actions, seed, counter, actions, (hipStream_t)stream);
     return err == hipSuccess ? SL_OK : hip_fail(err, "sample_actions_masked launch");
 }
 
@@ -1723,8 +1723,8 @@ int slhip_training_batch_multi(const sl_rollout_multi *buf, const float *final_v
     if (int rc = check_rollout_multi(buf)) return rc;
     if (buf->w.out_stride < buf->w.B) return fail(SL_E_ARG, "training_batch_multi: out_stride smaller than B");
     if (!final_values || !returns || !advantages) return fail(SL_E_ARG, "training_batch_multi: null pointer");
-    const hipError_t err = sl::launch_training_batch_multi(*buf, final_values, gamma, lmda, returns, advantages, traj_start,
-                                                           (hipStream_t)stream);
+    const hipError_t err = sl::launch_training_batch(buf->w, buf->active, final_values, gamma, lmda, returns, advantages,
+                                                     traj_start, (hipStream_t)stream);
     return err == hipSuccess ? SL_OK : hip_fail(err, "training_batch_multi launch");
 }
 

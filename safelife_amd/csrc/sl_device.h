@@ -167,6 +167,45 @@ __device__ __forceinline__ u64 draw_threshold(double p) {
     return (u64)ceil(p * 9007199254740992.0);
 }
 
+// ---- the action draws (slhip_sample_actions*, slhip_replay_sample) ----------------------------------------------------
+
+// z of draw i under (seed, counter): splitmix64's finalizer of seed + G * (counter * K + i + 1)
+__device__ __forceinline__ u64 draw_hash(u64 seed, u64 counter, u64 i) {
+    u64 z = seed + 0x9E3779B97F4A7C15ull * (counter * 0x100000001B3ull + i + 1ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// the top 24 bits of z as a float32 in [0, 1)
+__device__ __forceinline__ float draw_uniform24(u64 z) { return (float)(unsigned)(z >> 40) * (1.0f / 16777216.0f); }
+
+// ---- workgroup scan ----------------------------------------------------------------------------------------------------
+
+// Exclusive prefix of x over the THREADS lanes of the workgroup, and the workgroup's total: an inclusive scan inside each
+// wavefront, the wave totals through LDS (wave_sum: THREADS / 64 ints).  Every lane of the workgroup calls it; it ends
+// with a barrier, so wave_sum may be used again at once.
+template <int THREADS>
+__device__ __forceinline__ int block_exclusive_scan(int x, int *wave_sum, int &total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = x;
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(incl, o);
+        if (lane >= o) incl += y;
+    }
+    if (lane == 63) wave_sum[wave] = incl;
+    __syncthreads();
+    int before = 0;
+    total = 0;
+    for (int k = 0; k < THREADS / 64; ++k) {
+        const int s = wave_sum[k];
+        before += k < wave ? s : 0;
+        total += s;
+    }
+    __syncthreads();
+    return before + incl - x;
+}
+
 __device__ __forceinline__ int pos_mod(int a, int n) {
     int r = a % n;
     return r < 0 ? r + n : r;

@@ -1051,44 +1051,6 @@ __global__ __launch_bounds__(256) void k_obs_to_policy(const u32 *__restrict__ v
 
 // ------------------------------------------------------------------------------ launchers
 
-// One categorical draw per env from the policy's probabilities (training/ppo.py:66-69 draws on the host with numpy):
-// u = a 24-bit uniform from splitmix64(seed, counter, env); cum_k = the fp32 running sum p_0 + ... + p_k over ALL A
-// entries, in index order.  The action is the first k with u < cum_k; if there is none (the fp32 sum of a row can stay
-// below 1 while u reaches 1 - 2^-24), the largest k with p_k > 0, which takes what rounding leaves; A-1 only when no
-// entry is positive.  So an action of probability zero is never drawn while any entry is positive, and the result is
-// in [0, A) whatever the row holds (NaN, inf, negative entries).  z = seed + G * (counter * K + e + 1): a caller that
-// holds envs [lo, hi) of a larger batch passes seed + G * lo (mod 2^64) and gets the draws of envs lo + e of the whole.
-// One thread per env; the result goes straight into the int32 buffer the step reads.
-__global__ __launch_bounds__(256) void k_sample_actions(const float *__restrict__ probs, int B, int A, unsigned long long seed,
-                                                        unsigned long long counter, int32_t *__restrict__ actions) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= B) return;
-    unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (counter * 0x100000001B3ull + (unsigned long long)e + 1ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    const float u = (float)(unsigned)(z >> 40) * (1.0f / 16777216.0f);
-    const float *p = probs + (size_t)e * A;
-    float cum = 0.0f;
-    int a = A - 1;                  // the largest k with p_k > 0 seen so far (A-1 while there is none)
-    for (int k = 0; k < A; ++k) {
-        const float pk = p[k];
-        cum += pk;
-        if (pk > 0.0f) a = k;
-        if (u < cum) {
-            a = k;
-            break;
-        }
-    }
-    actions[e] = a;
-}
-
-hipError_t launch_sample_actions(const float *probs, int B, int A, unsigned long long seed, unsigned long long counter,
-                                 int32_t *actions, hipStream_t stream) {
-    hipLaunchKernelGGL(k_sample_actions, dim3((B + 255) / 256), dim3(256), 0, stream, probs, B, A, seed, counter, actions);
-    return hipGetLastError();
-}
-
 hipError_t launch_obs_to_policy(const u32 *view, int B, int vh, int vw, const sl_channel_list &ch, int C, void *out,
                                 int dtype, hipStream_t stream) {
     const long long total = (long long)B * C * vw * vh;

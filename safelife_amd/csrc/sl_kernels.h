@@ -41,8 +41,6 @@ hipError_t launch_multi_baseline(const sl_env_batch &env, const sl_multi_agent &
 struct sl_channel_list {
     int32_t c[SL_MAX_CHANNELS];
 };
-hipError_t launch_sample_actions(const float *probs, int B, int A, unsigned long long seed, unsigned long long counter,
-                                 int32_t *actions, hipStream_t stream);
 hipError_t launch_obs_to_policy(const u32 *view, int B, int vh, int vw, const sl_channel_list &ch, int C, void *out,
                                 int dtype, hipStream_t stream);
 
@@ -81,19 +79,17 @@ hipError_t launch_emd(const sl_episode_queue &q, int H, int W, int num_samples, 
                       void *workspace, int concurrency, double *scores, int32_t *n_cells, hipStream_t stream);
 // sl_render.hip : boards -> RGB frames (variant: 0 the default, 1 cells decoded by every lane, 2 cells staged in LDS)
 hipError_t launch_render(const sl_render_args &args, int variant, hipStream_t stream);
-// sl_rollout.hip : the rollout buffer's per-step record, and returns / GAE advantages of a window (PPO.gen_training_batch)
+// sl_rollout.hip : PPO's window -- the categorical draw (active null: every row), the per-step record, returns / GAE
+// advantages (PPO.gen_training_batch; active null: the plain window), and the masked window's compaction and gather
+hipError_t launch_sample_actions(const float *probs, const uint8_t *active, int B, int A, unsigned long long seed,
+                                 unsigned long long counter, int32_t *actions, hipStream_t stream);
 hipError_t launch_rollout_record(const sl_rollout &buf, int t, const int32_t *actions, const float *probs, int n_actions,
                                  const void *rewards, const float *values, const uint8_t *done, hipStream_t stream);
-hipError_t launch_training_batch(const sl_rollout &buf, const float *final_values, double gamma, double lmda,
-                                 float *returns, float *advantages, uint8_t *traj_start, hipStream_t stream);
-// sl_rollout_multi.hip : the masked window of multi-agent envs -- masked draw, record, returns / GAE, compaction, gather
-hipError_t launch_sample_actions_masked(const float *probs, const uint8_t *active, int B, int A, unsigned long long seed,
-                                        unsigned long long counter, int32_t *actions, hipStream_t stream);
 hipError_t launch_rollout_record_multi(const sl_rollout_multi &buf, int t, const int32_t *actions, const float *probs,
                                        int n_actions, const void *rewards, const float *values, const uint8_t *done,
                                        uint8_t *active_now, long long *num_resets, hipStream_t stream);
-hipError_t launch_training_batch_multi(const sl_rollout_multi &buf, const float *final_values, double gamma, double lmda,
-                                       float *returns, float *advantages, uint8_t *traj_start, hipStream_t stream);
+hipError_t launch_training_batch(const sl_rollout &buf, const uint8_t *active, const float *final_values, double gamma,
+                                 double lmda, float *returns, float *advantages, uint8_t *traj_start, hipStream_t stream);
 int rollout_compact_chunks(const sl_rollout_multi &buf);
 hipError_t launch_rollout_compact(const sl_rollout_multi &buf, long long *rows_out, long long *count_out, int32_t *workspace,
                                   hipStream_t stream);

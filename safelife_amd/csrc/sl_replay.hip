@@ -16,6 +16,7 @@
 // The window is a ring over t mod n shared by all envs, so slot *head (where this step goes) is also the slot of the
 // step n steps back: every lane reads its piece of the old row before it writes the new one to the same address.
 #include "sl_kernels.h"
+#include "sl_rows.h"
 
 #pragma clang fp contract(off)
 
@@ -25,18 +26,9 @@ namespace {
 constexpr int PLAN_THREADS = 1024;
 constexpr int ROW_THREADS = 256;
 
-__device__ __forceinline__ unsigned long long replay_z(unsigned long long seed, unsigned long long counter,
-                                                       unsigned long long i) {
-    // the draw of k_sample_actions (sl_generic.hip): splitmix64's finalizer of seed + G * (counter * K + i + 1)
-    unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (counter * 0x100000001B3ull + i + 1ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 __global__ __launch_bounds__(PLAN_THREADS) void k_replay_plan(sl_replay buf, const uint8_t *__restrict__ done) {
     __shared__ int wave_sum[PLAN_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int B = buf.B, n = buf.n;
     const long long cap = buf.capacity;
     const long long idx0 = *buf.idx;
@@ -55,26 +47,14 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_replay_plan(sl_replay buf, con
             buf.fill[b] = d ? 0 : fn;
             buf.plan_code[b] = f | (d << 8);
         }
-        int x = cnt;                            // inclusive scan inside the wave
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(x, o);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) wave_sum[wave] = x;
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int w = 0; w < PLAN_THREADS / 64; ++w) {
-            const int s = wave_sum[w];
-            before += w < wave ? s : 0;
-            total += s;
-        }
+        int total;
+        const int before = block_exclusive_scan<PLAN_THREADS>(cnt, wave_sum, total);
         if (b < B) {
-            long long s = start + carry + before + (x - cnt);       // < 2 * cap: one step pushes at most B * (n+1) <= cap
+            long long s = start + carry + before;       // < 2 * cap: one step pushes at most B * (n+1) <= cap
             if (s >= cap) s -= cap;
             buf.plan_base[b] = s;
         }
         carry += total;
-        __syncthreads();
     }
     if (tid == 0) {
         *buf.idx = idx0 + carry;
@@ -185,7 +165,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_replay_sample(sl_replay buf, i
     }
     const unsigned long long base = (unsigned long long)(N - k);
     for (int i = tid; i < k; i += PLAN_THREADS)
-        ts[i] = __umul64hi(replay_z(seed, counter, (unsigned long long)i), base + (unsigned long long)i + 1ull);
+        ts[i] = __umul64hi(draw_hash(seed, counter, (unsigned long long)i), base + (unsigned long long)i + 1ull);
     __syncthreads();
     for (int i = tid; i < k; i += PLAN_THREADS) {
         const unsigned long long t = ts[i];
@@ -282,8 +262,8 @@ __global__ __launch_bounds__(256) void k_sample_actions_eps(const float *__restr
                                                             int32_t *__restrict__ actions) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= B) return;
-    const unsigned long long z = replay_z(seed, counter, (unsigned long long)e);
-    const float u = (float)(unsigned)(z >> 40) * (1.0f / 16777216.0f);
+    const unsigned long long z = draw_hash(seed, counter, (unsigned long long)e);
+    const float u = draw_uniform24(z);
     int a;
     if ((double)u < epsilon) {
         a = (int)(((z & 0xFFFFFFFFull) * (unsigned long long)A) >> 32);
@@ -303,13 +283,6 @@ __global__ __launch_bounds__(256) void k_sample_actions_eps(const float *__restr
     actions[e] = a;
 }
 
-// the widest of 16 / 8 / 4 / 2 / 1 bytes that divides the row size and every row pointer
-int row_align(long long obs_bytes, std::initializer_list<const void *> ptrs) {
-    unsigned long long bits = (unsigned long long)obs_bytes | 16ull;
-    for (const void *p : ptrs) bits |= (unsigned long long)(uintptr_t)p;
-    return (int)(bits & (~bits + 1ull));
-}
-
 }  // namespace
 
 hipError_t launch_replay_add(const sl_replay &buf, const void *obs, const int32_t *actions, const void *rewards,
@@ -318,16 +291,11 @@ hipError_t launch_replay_add(const sl_replay &buf, const void *obs, const int32_
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
     const dim3 grid((unsigned)buf.B), block(ROW_THREADS);
-    switch (row_align(buf.obs_bytes, {obs, next_obs, buf.obs, buf.next_obs, buf.win_obs})) {
-#define SL_REPLAY_COPY(V) \
-    hipLaunchKernelGGL(k_replay_copy<V>, grid, block, 0, stream, buf, (const V *)obs, actions, rewards, (const V *)next_obs)
-    case 16: SL_REPLAY_COPY(uint4); break;
-    case 8: SL_REPLAY_COPY(uint2); break;
-    case 4: SL_REPLAY_COPY(uint32_t); break;
-    case 2: SL_REPLAY_COPY(uint16_t); break;
-    default: SL_REPLAY_COPY(uint8_t); break;
-#undef SL_REPLAY_COPY
-    }
+    with_row_type(row_align(buf.obs_bytes, {obs, next_obs, buf.obs, buf.next_obs, buf.win_obs}), [&](auto v) {
+        typedef decltype(v) V;
+        hipLaunchKernelGGL(k_replay_copy<V>, grid, block, 0, stream, buf, (const V *)obs, actions, rewards,
+                           (const V *)next_obs);
+    });
     return hipGetLastError();
 }
 
@@ -346,26 +314,20 @@ hipError_t launch_replay_gather(const sl_replay &buf, const long long *index, in
         // row size and the outputs are 16-byte aligned
         int a = row_align(buf.obs_bytes, {buf.obs, buf.next_obs});
         if (row_align(16, {obs_out, next_obs_out}) < 16) a = 1;
-#define SL_REPLAY_WIDEN(U) \
-    hipLaunchKernelGGL(k_replay_gather_f32<U>, grid, block, 0, stream, buf, index, (float *)obs_out, (float *)next_obs_out, \
-                       action_out, reward_out, done_out)
-        if (a >= 4) SL_REPLAY_WIDEN(4);
-        else if (a == 2) SL_REPLAY_WIDEN(2);
-        else SL_REPLAY_WIDEN(1);
-#undef SL_REPLAY_WIDEN
+        const auto widen = [&](auto u) {
+            hipLaunchKernelGGL(k_replay_gather_f32<(int)sizeof(u)>, grid, block, 0, stream, buf, index, (float *)obs_out,
+                               (float *)next_obs_out, action_out, reward_out, done_out);
+        };
+        if (a >= 4) widen(uint32_t());
+        else if (a == 2) widen(uint16_t());
+        else widen(uint8_t());
         return hipGetLastError();
     }
-    switch (row_align(buf.obs_bytes, {buf.obs, buf.next_obs, obs_out, next_obs_out})) {
-#define SL_REPLAY_GATHER(V) \
-    hipLaunchKernelGGL(k_replay_gather<V>, grid, block, 0, stream, buf, index, (V *)obs_out, (V *)next_obs_out, action_out, \
-                       reward_out, done_out)
-    case 16: SL_REPLAY_GATHER(uint4); break;
-    case 8: SL_REPLAY_GATHER(uint2); break;
-    case 4: SL_REPLAY_GATHER(uint32_t); break;
-    case 2: SL_REPLAY_GATHER(uint16_t); break;
-    default: SL_REPLAY_GATHER(uint8_t); break;
-#undef SL_REPLAY_GATHER
-    }
+    with_row_type(row_align(buf.obs_bytes, {buf.obs, buf.next_obs, obs_out, next_obs_out}), [&](auto v) {
+        typedef decltype(v) V;
+        hipLaunchKernelGGL(k_replay_gather<V>, grid, block, 0, stream, buf, index, (V *)obs_out, (V *)next_obs_out,
+                           action_out, reward_out, done_out);
+    });
     return hipGetLastError();
 }
 

@@ -28,50 +28,39 @@ TrainingBatch = collections.namedtuple("TrainingBatch", "obs actions action_prob
 DenseTrainingBatch = collections.namedtuple("DenseTrainingBatch", TrainingBatch._fields + ("valid",))
 
 
-class RolloutBuffer(object):
-    """
-    Parameters
-    ----------
-    num_envs, steps : int        B and T of the window
-    obs_shape, obs_dtype         shape of ONE env's observation and its torch dtype: ``obs`` is ``[T, B, *obs_shape]``
-                                 (None: no observation store, ``finish().obs`` is None)
-    reward_dtype                 torch.float32 (``env.reward``) or torch.float64 (``env.shaped_reward`` under wrappers)
-    device                       the torch device
-    traj_start : bool            also keep ``traj_start`` uint8 [T, B] (written by ``finish``)
-    """
+class _Window(object):
+    """What the two buffers share: the time-major ``[T, N]`` tensors of a window of N columns, ``struct sl_rollout`` filled
+    from them, the conversion of a step's fields into what the record kernels read, their call, and the status word."""
 
-    def __init__(self, num_envs, steps, obs_shape=None, obs_dtype=None, reward_dtype=None, device=None, traj_start=True):
+    _bad_action = None                  # check_status()'s message for ROLLOUT_BAD_ACTION
+
+    def _allocate(self, struct, T, N, obs_shape, obs_dtype, reward_dtype, device, traj_start=True):
+        """The window's tensors as attributes, and ``struct`` (the ``sl_rollout`` to fill) pointing at them."""
         import torch
         self.torch = torch
-        T, B = int(steps), int(num_envs)
-        if T < 1 or B < 1:
-            raise ValueError("RolloutBuffer needs steps >= 1 and num_envs >= 1")
         reward_dtype = torch.float32 if reward_dtype is None else reward_dtype
         if reward_dtype not in (torch.float32, torch.float64):
             raise ValueError("reward_dtype must be torch.float32 or torch.float64")
         self.device = dev = _hip.device() if device is None else torch.device(device)
-        self.num_envs, self.steps, self.reward_dtype = B, T, reward_dtype
+        self.steps, self.reward_dtype = T, reward_dtype
         self.obs = None
         if obs_shape is not None:
-            self.obs = torch.zeros((T, B) + tuple(obs_shape), dtype=obs_dtype or torch.float32, device=dev)
-        self.actions = torch.zeros((T, B), dtype=torch.int32, device=dev)
-        self.action_prob = torch.zeros((T, B), dtype=torch.float32, device=dev)
-        self.rewards = torch.zeros((T, B), dtype=reward_dtype, device=dev)
-        self.values = torch.zeros((T, B), dtype=torch.float32, device=dev)
-        self.done = torch.zeros((T, B), dtype=torch.uint8, device=dev)
-        self.returns = torch.zeros((T, B), dtype=torch.float32, device=dev)
-        self.advantages = torch.zeros((T, B), dtype=torch.float32, device=dev)
-        self.traj_start = torch.zeros((T, B), dtype=torch.uint8, device=dev) if traj_start else None
-        #: device word: bit ROLLOUT_BAD_ACTION is raised by a recorded action outside [0, n_actions)
+            self.obs = torch.zeros((T, N) + tuple(obs_shape), dtype=obs_dtype or torch.float32, device=dev)
+        self.actions = torch.zeros((T, N), dtype=torch.int32, device=dev)
+        self.action_prob = torch.zeros((T, N), dtype=torch.float32, device=dev)
+        self.rewards = torch.zeros((T, N), dtype=reward_dtype, device=dev)
+        self.values = torch.zeros((T, N), dtype=torch.float32, device=dev)
+        self.done = torch.zeros((T, N), dtype=torch.uint8, device=dev)
+        self.returns = torch.zeros((T, N), dtype=torch.float32, device=dev)
+        self.advantages = torch.zeros((T, N), dtype=torch.float32, device=dev)
+        self.traj_start = torch.zeros((T, N), dtype=torch.uint8, device=dev) if traj_start else None
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         self._lib = _hip.lib()
-        s = self.struct = _hip.Rollout()
-        s.T, s.B = T, B
-        s.reward_dtype = _hip.REWARD_F64 if reward_dtype == torch.float64 else _hip.REWARD_F32
-        s.row_stride = s.out_stride = B
+        struct.T, struct.B = T, N
+        struct.reward_dtype = _hip.REWARD_F64 if reward_dtype == torch.float64 else _hip.REWARD_F32
+        struct.row_stride = struct.out_stride = N
         for name in ("actions", "action_prob", "rewards", "values", "done", "status"):
-            setattr(s, name, getattr(self, name).data_ptr())
-        self._sref = C.byref(s)
+            setattr(struct, name, getattr(self, name).data_ptr())
 
     def _as(self, x, dtype, shape):
         torch = self.torch
@@ -83,30 +72,72 @@ class RolloutBuffer(object):
         x = x.to(device=self.device, dtype=dtype).reshape(shape)
         return x if x.is_contiguous() else x.contiguous()
 
-    def record(self, t, step):
-        """Row ``t`` of the window from a ``StepResult`` (or any object with obs, actions, rewards, done, policies,
-        values): the observation with ``copy_``, the rest -- the action's own probability included -- with one kernel on
-        the current stream."""
-        torch, B = self.torch, self.num_envs
+    def _step_tensors(self, t, step, N):
+        """``t`` and the step's reward dtype checked; its actions, policies, rewards, values and done over the N columns
+        as the record kernels read them."""
+        torch = self.torch
         if not 0 <= t < self.steps:
             raise ValueError("t outside [0, steps)")
         if step.rewards.dtype != self.reward_dtype:
             raise ValueError("rewards are %s, the buffer was built for %s" % (step.rewards.dtype, self.reward_dtype))
-        if self.obs is not None:
-            self.obs[t].copy_(step.obs)
-        actions = self._as(step.actions, torch.int32, (B,))
-        probs = self._as(step.policies, torch.float32, (B, -1))
-        rewards = self._as(step.rewards, self.reward_dtype, (B,))
-        values = self._as(step.values, torch.float32, (B,))
         done = step.done
         if torch.is_tensor(done) and done.dtype == torch.bool:
             done = done.view(torch.uint8)       # (a bool tensor is one byte of 0 / 1 per element)
-        done = self._as(done, torch.uint8, (B,))
-        rc = self._lib.slhip_rollout_record(self._sref, int(t), _hip.ptr(actions), _hip.ptr(probs), probs.shape[1],
-                                            _hip.ptr(rewards), _hip.ptr(values), _hip.ptr(done),
-                                            _hip.current_stream_ptr())
+        return (self._as(step.actions, torch.int32, (N,)), self._as(step.policies, torch.float32, (N, -1)),
+                self._as(step.rewards, self.reward_dtype, (N,)), self._as(step.values, torch.float32, (N,)),
+                self._as(done, torch.uint8, (N,)))
+
+    def _record(self, entry, t, tensors, *more):
+        """One of the record entry points on row ``t``, on the current stream."""
+        actions, probs, rewards, values, done = tensors
+        rc = entry(self._sref, int(t), _hip.ptr(actions), _hip.ptr(probs), probs.shape[1], _hip.ptr(rewards),
+                   _hip.ptr(values), _hip.ptr(done), *more, _hip.current_stream_ptr())
         if rc:
             _hip.check(rc)
+
+    def check_status(self):
+        """Read the status word (a host visit) and raise on a recorded action outside the policy's range or, where rows
+        are gathered by id, a bad row id."""
+        word = int(self.status.item())
+        if word & _hip.ROLLOUT_BAD_ACTION:
+            raise ValueError(self._bad_action)
+        if word & _hip.ROLLOUT_BAD_INDEX:
+            raise ValueError("%s: a row id outside the window was gathered" % type(self).__name__)
+
+
+class RolloutBuffer(_Window):
+    """
+    Parameters
+    ----------
+    num_envs, steps : int        B and T of the window
+    obs_shape, obs_dtype         shape of ONE env's observation and its torch dtype: ``obs`` is ``[T, B, *obs_shape]``
+                                 (None: no observation store, ``finish().obs`` is None)
+    reward_dtype                 torch.float32 (``env.reward``) or torch.float64 (``env.shaped_reward`` under wrappers)
+    device                       the torch device
+    traj_start : bool            also keep ``traj_start`` uint8 [T, B] (written by ``finish``)
+
+    ``status`` is a device word: bit ROLLOUT_BAD_ACTION is raised by a recorded action outside [0, n_actions).
+    """
+
+    _bad_action = "RolloutBuffer: an action outside [0, n_actions) was recorded (its probability reads 0)"
+
+    def __init__(self, num_envs, steps, obs_shape=None, obs_dtype=None, reward_dtype=None, device=None, traj_start=True):
+        T, B = int(steps), int(num_envs)
+        if T < 1 or B < 1:
+            raise ValueError("RolloutBuffer needs steps >= 1 and num_envs >= 1")
+        self.num_envs = B
+        self.struct = _hip.Rollout()
+        self._allocate(self.struct, T, B, obs_shape, obs_dtype, reward_dtype, device, traj_start)
+        self._sref = C.byref(self.struct)
+
+    def record(self, t, step):
+        """Row ``t`` of the window from a ``StepResult`` (or any object with obs, actions, rewards, done, policies,
+        values): the observation with ``copy_``, the rest -- the action's own probability included -- with one kernel on
+        the current stream."""
+        tensors = self._step_tensors(t, step, self.num_envs)
+        if self.obs is not None:
+            self.obs[t].copy_(step.obs)
+        self._record(self._lib.slhip_rollout_record, t, tensors)
 
     def finish(self, final_values, gamma=0.97, lmda=0.95):
         """Returns and advantages of the recorded window; the reference's ``named_output`` of ``gen_training_batch``:
@@ -124,13 +155,8 @@ class RolloutBuffer(object):
         return TrainingBatch(obs, self.actions.view(T * B).to(torch.int64), self.action_prob.view(T * B),
                              self.returns.view(T * B), self.advantages.view(T * B), self.values.view(T * B))
 
-    def check_status(self):
-        """Read the status word (a host visit) and raise if a recorded action lay outside the policy's range."""
-        if int(self.status.item()) & _hip.ROLLOUT_BAD_ACTION:
-            raise ValueError("RolloutBuffer: an action outside [0, n_actions) was recorded (its probability reads 0)")
 
-
-class MultiAgentRolloutBuffer(object):
+class MultiAgentRolloutBuffer(_Window):
     """
     A window of ``MultiAgentRunner`` steps: ``[T, B * A]`` columns, column ``b * A + a`` being agent ``a`` of env ``b``,
     with ``active`` uint8 ``[T, B * A]`` next to the arrays of ``RolloutBuffer``.  The state the reference carries from
@@ -144,88 +170,44 @@ class MultiAgentRolloutBuffer(object):
                                         ``[T, B * A, *obs_shape]`` (None: no observation store)
     reward_dtype                        torch.float32 (the multi-agent env's ``reward`` and ``shaped_reward``) or float64
     device                              the torch device
+
+    ``status`` is a device word: ROLLOUT_BAD_ACTION (an active agent's action outside [0, n_actions)), ROLLOUT_BAD_INDEX.
     """
 
+    _bad_action = "MultiAgentRolloutBuffer: an active agent's action lay outside [0, n_actions)"
+
     def __init__(self, num_envs, n_agents, steps, obs_shape=None, obs_dtype=None, reward_dtype=None, device=None):
-        import torch
-        self.torch = torch
         T, B, A = int(steps), int(num_envs), int(n_agents)
         if T < 1 or B < 1 or not 1 <= A <= _hip.SL_MAX_AGENTS:
             raise ValueError("MultiAgentRolloutBuffer needs steps >= 1, num_envs >= 1 and 1 <= n_agents <= %d"
                              % _hip.SL_MAX_AGENTS)
-        reward_dtype = torch.float32 if reward_dtype is None else reward_dtype
-        if reward_dtype not in (torch.float32, torch.float64):
-            raise ValueError("reward_dtype must be torch.float32 or torch.float64")
-        self.device = dev = _hip.device() if device is None else torch.device(device)
-        self.num_envs, self.n_agents, self.steps, self.reward_dtype = B, A, T, reward_dtype
+        self.num_envs, self.n_agents = B, A
         N = self.columns = B * A
-        self.obs = None
-        if obs_shape is not None:
-            self.obs = torch.zeros((T, N) + tuple(obs_shape), dtype=obs_dtype or torch.float32, device=dev)
-        self.actions = torch.zeros((T, N), dtype=torch.int32, device=dev)
-        self.action_prob = torch.zeros((T, N), dtype=torch.float32, device=dev)
-        self.rewards = torch.zeros((T, N), dtype=reward_dtype, device=dev)
-        self.values = torch.zeros((T, N), dtype=torch.float32, device=dev)
-        self.done = torch.zeros((T, N), dtype=torch.uint8, device=dev)
+        m = self.struct = _hip.RolloutMulti()
+        self._allocate(m.w, T, N, obs_shape, obs_dtype, reward_dtype, device)
+        torch, dev = self.torch, self.device
         self.active = torch.zeros((T, N), dtype=torch.uint8, device=dev)
-        self.returns = torch.zeros((T, N), dtype=torch.float32, device=dev)
-        self.advantages = torch.zeros((T, N), dtype=torch.float32, device=dev)
-        self.traj_start = torch.zeros((T, N), dtype=torch.uint8, device=dev)
         #: num_resets of every env DURING step t (the middle entry of the reference's agent ids)
         self.resets_at = torch.zeros((T, B), dtype=torch.int64, device=dev)
         self.active_now = torch.ones((B, A), dtype=torch.uint8, device=dev)
         self.num_resets = torch.zeros(B, dtype=torch.int64, device=dev)
-        #: device word: ROLLOUT_BAD_ACTION (an active agent's action outside [0, n_actions)), ROLLOUT_BAD_INDEX
-        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         self.rows_all = torch.zeros(T * N, dtype=torch.int64, device=dev)
         self.count = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._lib = _hip.lib()
-        m = self.struct = _hip.RolloutMulti()
-        s = m.w
-        s.T, s.B = T, N
-        s.reward_dtype = _hip.REWARD_F64 if reward_dtype == torch.float64 else _hip.REWARD_F32
-        s.row_stride = s.out_stride = N
-        for name in ("actions", "action_prob", "rewards", "values", "done", "status"):
-            setattr(s, name, getattr(self, name).data_ptr())
         m.n_agents, m.active = A, self.active.data_ptr()
         self._sref = C.byref(m)
         self._scan = torch.zeros(self._lib.slhip_rollout_compact_chunks(self._sref), dtype=torch.int32, device=dev)
         self.rows = self.agent_ids = None
-
-    def _as(self, x, dtype, shape):
-        torch = self.torch
-        if not torch.is_tensor(x):
-            x = torch.as_tensor(x)
-        x = x.to(device=self.device, dtype=dtype).reshape(shape)
-        return x if x.is_contiguous() else x.contiguous()
 
     def record(self, t, step):
         """Row ``t`` of the window from a step of all ``B * A`` agents (an object with obs, actions, rewards, done,
         policies, values shaped ``[B, A, ...]`` or ``[B * A, ...]``).  What ``active_now`` says decides which columns are
         kept -- the others record zeros, whatever the step holds for them -- and then ``active_now`` / ``num_resets``
         move on to the next step.  The observation goes with ``copy_``, everything else with one kernel."""
-        torch, N = self.torch, self.columns
-        if not 0 <= t < self.steps:
-            raise ValueError("t outside [0, steps)")
-        if step.rewards.dtype != self.reward_dtype:
-            raise ValueError("rewards are %s, the buffer was built for %s" % (step.rewards.dtype, self.reward_dtype))
+        tensors = self._step_tensors(t, step, self.columns)
         if self.obs is not None:
             self.obs[t].copy_(step.obs.reshape(self.obs.shape[1:]))
         self.resets_at[t].copy_(self.num_resets)
-        actions = self._as(step.actions, torch.int32, (N,))
-        probs = self._as(step.policies, torch.float32, (N, -1))
-        rewards = self._as(step.rewards, self.reward_dtype, (N,))
-        values = self._as(step.values, torch.float32, (N,))
-        done = step.done
-        if torch.is_tensor(done) and done.dtype == torch.bool:
-            done = done.view(torch.uint8)
-        done = self._as(done, torch.uint8, (N,))
-        rc = self._lib.slhip_rollout_record_multi(self._sref, int(t), _hip.ptr(actions), _hip.ptr(probs), probs.shape[1],
-                                                  _hip.ptr(rewards), _hip.ptr(values), _hip.ptr(done),
-                                                  _hip.ptr(self.active_now), _hip.ptr(self.num_resets),
-                                                  _hip.current_stream_ptr())
-        if rc:
-            _hip.check(rc)
+        self._record(self._lib.slhip_rollout_record_multi, t, tensors, _hip.ptr(self.active_now), _hip.ptr(self.num_resets))
 
     def finish(self, final_values, gamma=0.97, lmda=0.95, gather_obs=True, dense=False):
         """Returns and advantages of the recorded window (``slhip_training_batch_multi``), then the reference's
@@ -279,11 +261,3 @@ class MultiAgentRolloutBuffer(object):
         t, b = torch.div(env, self.num_envs, rounding_mode="floor"), env % self.num_envs
         self.agent_ids = torch.stack([b, self.resets_at[t, b], rows % A], dim=1)
         return TrainingBatch(obs, actions, prob, ret, adv, val)
-
-    def check_status(self):
-        """Read the status word (a host visit) and raise on a recorded action outside the policy's range or a bad row id."""
-        word = int(self.status.item())
-        if word & _hip.ROLLOUT_BAD_ACTION:
-            raise ValueError("MultiAgentRolloutBuffer: an active agent's action lay outside [0, n_actions)")
-        if word & _hip.ROLLOUT_BAD_INDEX:
-            raise ValueError("MultiAgentRolloutBuffer: a row id outside the window was gathered")

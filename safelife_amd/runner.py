@@ -26,6 +26,13 @@ MultiAgentStep = collections.namedtuple("MultiAgentStep", StepResult._fields + (
 _SPLITMIX_G = 0x9E3779B97F4A7C15        # the increment of the draw kernel's splitmix64 (slhip_sample_actions)
 
 
+def _model_in(obs, cast_obs):
+    """What the model is handed: float32 (training/ppo.py:64, dqn.py:97), or with ``cast_obs=False`` the env's tensor as
+    it is (a uint8 policy tensor stays uint8)."""
+    import torch
+    return obs if (obs.dtype == torch.float32 or not cast_obs) else obs.to(torch.float32)
+
+
 class VectorRunner(object):
     """
     Parameters
@@ -85,10 +92,8 @@ class VectorRunner(object):
         the fused step."""
         torch = self.torch
         obs, agent_ids = self.obs_for_envs()
-        # (training/ppo.py:64 hands the network float32; cast_obs=False leaves a uint8 policy tensor as it is)
-        model_in = obs if (obs.dtype == torch.float32 or not self.cast_obs) else obs.to(torch.float32)
         with torch.no_grad():
-            values, policies = self.policy(model_in)
+            values, policies = self.policy(_model_in(obs, self.cast_obs))
         actions = torch.multinomial(policies, 1, generator=self.generator).squeeze(1)
         kept = obs.clone() if self.copy_obs else obs
         next_obs, rewards, done = self.act_on_envs(actions)
@@ -125,10 +130,8 @@ class VectorRunner(object):
                 buf.record(t, step)
         finally:
             self.copy_obs = copy_obs
-        nxt = step.next_obs
-        model_in = nxt if (nxt.dtype == torch.float32 or not self.cast_obs) else nxt.to(torch.float32)
         with torch.no_grad():
-            final_values = self.policy(model_in)[0]
+            final_values = self.policy(_model_in(step.next_obs, self.cast_obs))[0]
         # training/ppo.py:134 counts agent steps: steps_per_env * len(training_envs)
         self.num_steps = steps_before + T * self.env.num_envs
         # (envs whose last step has `done` take 0.0 instead: the kernel looks at the flag itself)
@@ -177,9 +180,8 @@ class DQNRunner(object):
             self._started = True
         obs = env.policy_tensor
         agent_ids = (self.env_ids, self.num_resets.clone())
-        model_in = obs if (obs.dtype == torch.float32 or not self.cast_obs) else obs.to(torch.float32)
         with torch.no_grad():
-            qvals = self.q_model(model_in)
+            qvals = self.q_model(_model_in(obs, self.cast_obs))
         if qvals.dtype != torch.float32 or not qvals.is_contiguous():
             qvals = qvals.to(torch.float32).contiguous()
         if qvals.dim() != 2 or qvals.shape[0] != env.num_envs:
@@ -364,9 +366,7 @@ class MultiAgentRunner(object):
         return self._state.num_resets
 
     def _model_in(self, obs):
-        torch = self.torch
-        x = obs.view((-1,) + tuple(obs.shape[2:]))
-        return x if (x.dtype == torch.float32 or not self.cast_obs) else x.to(torch.float32)
+        return _model_in(obs.view((-1,) + tuple(obs.shape[2:])), self.cast_obs)
 
     def _step(self):
         """Model, masked draw, fused step -- everything but the bookkeeping, which ``record_multi`` does."""

@@ -1,5 +1,5 @@
 """
-The device action draw (slhip_sample_actions, k_sample_actions in csrc/sl_generic.hip) restated on the host, and the
+The device action draw (slhip_sample_actions, k_sample_actions in csrc/sl_rollout.hip) restated on the host, and the
 high-precision reference it is held against.  numpy only; nothing here loads the library.
 
 ``draw_u24`` / ``sample_model`` are an EXACT model: the kernel's integer arithmetic in np.uint64 (wrapping) and its

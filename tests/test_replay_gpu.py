@@ -119,6 +119,43 @@ def test_add_through_other_layouts_and_dtypes():
         buf.add(Step(step.obs, step.actions, torch.zeros(B, dtype=other, device=dev), step.done, step.next_obs))
 
 
+def test_add_across_the_plan_kernels_chunk_boundary():
+    """B = 1030 envs: the plan kernel scans them in chunks of 1024 and carries the pushes of the first chunk into the
+    slots of the second.  n = 2, four steps, 16-byte rows, done flags on both sides of the boundary at every step; ring,
+    idx and fill against the numpy restatement."""
+    import torch
+    from safelife_amd.replay import ReplayBuffer
+    dev = _hip.device()
+    B, n, T, nbytes, gamma = 1030, 2, 4, 16, 0.97
+    cap = 2 * B * (n + 1)                               # no wrap: 4 steps push at most 4 * B rows
+    envs = np.arange(B)
+    rng = np.random.default_rng(1030)
+    buf = ReplayBuffer(cap, B, multi_step=n, gamma=gamma, obs_shape=(nbytes,), obs_dtype=torch.uint8,
+                       reward_dtype=torch.float32, device=dev)
+    rep = rr.Replay(cap, B, n, gamma)
+    for t in range(T):
+        done = ((envs * 7 + t * 3) % 5 == 0).astype(np.uint8)
+        assert done[:1024].any() and done[1024:].any() and not done[1024:].all()
+        actions = rng.integers(0, 9, B).astype(np.int32)
+        rewards = rng.normal(0, 3, B).astype(np.float32)
+        obs, nxt = rows_of(envs, t, nbytes), rows_of(envs, t + 1, nbytes)
+        before = rep.idx
+        rep.add([r.tobytes() for r in obs], actions, rewards, done, [r.tobytes() for r in nxt])
+        buf.add(Step(*(torch.from_numpy(x).to(dev) for x in (obs, actions, rewards, done, nxt))))
+        assert int(buf.idx.item()) == rep.idx > before, t
+    size = rep.idx
+    assert size < cap and len(buf) == size
+    assert np.array_equal(buf.fill.cpu().numpy(), rep.fill())
+    obs, nxt = buf.obs.cpu().numpy(), buf.next_obs.cpu().numpy()
+    act, rew, done = buf.action.cpu().numpy(), buf.reward.cpu().numpy(), buf.done.cpu().numpy()
+    for s in range(size):
+        o, a, r, no, d = rep.ring[s]
+        assert obs[s].tobytes() == o and nxt[s].tobytes() == no and act[s] == a and done[s] == d, s
+        assert bits64(rew[s]) == bits64(r), s
+    assert not obs[size:].any() and not nxt[size:].any()
+    assert int(buf.status.item()) == 0
+
+
 # ---------------------------------------------------------------------------------------------------------- the sampler
 
 def _sized_buffer(N, capacity=None):

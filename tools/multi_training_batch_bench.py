@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """
-Times the multi-agent PPO batch builder (csrc/sl_rollout_multi.hip) at T = 20 and 8192 / 16384 columns, float32 rewards:
+Times the multi-agent PPO batch builder (the masked window of csrc/sl_rollout.hip) at T = 20 and 8192 / 16384 columns, float32 rewards:
 
     (a) slhip_training_batch_multi with every row active against slhip_training_batch on the same window (the outputs
         are checked to be bit-equal first): what the mask costs when nobody is ever away
