@@ -808,7 +808,7 @@ typedef struct sl_replay {        /* 264 bytes */
     long long *idx;               /* one device int64, zeroed by the caller: pushes so far */
     int32_t *status;              /* one device word, zeroed by the caller; the kernels only ever set bits (SL_REPLAY_*) */
     long long *plan_base;         /* workspace [B]: the first ring slot (before the modulo) of each env's pushes */
-    int32_t *plan_code;           /* workspace [B]: fill before the step | done << 8 */
+    int32_t *plan_code;           /* workspace [B]: fill before the step | done << 8 | inactive << 9 */
 } sl_replay;
 
 /* add_to_replay for one step of all B envs.  obs, next_obs: [B, obs_bytes]; actions: int32 [B]; rewards: [B] of
@@ -817,6 +817,25 @@ typedef struct sl_replay {        /* 264 bytes */
  * updates the window and moves the rows. */
 int slhip_replay_add(const sl_replay *buf, const void *obs, const int32_t *actions, const void *rewards,
                      const uint8_t *done, const void *next_obs, void *stream);
+
+/* slhip_replay_add for envs with several agents (additive to ABI 13, like slhip_sample_actions_eps_masked below).  The
+ * reference's DQN is handed only the agents that are still active, env-major, agent-minor; a trajectory window belongs to
+ * (env, num_resets, agent), an agent that is done has its window flushed and takes no further part until its env is
+ * reset, which happens once ALL its agents are done (training/base_algo.py:152-244, dqn.py:110-134).  Here buf->B is the
+ * number of COLUMNS, envs * n_agents, column e * n_agents + a being agent a of env e (the layout of sl_rollout_multi), and
+ * active: uint8 [B] says who took part in this step (NULL: everybody -- the result is then slhip_replay_add's bit for bit).
+ *   A column with active == 0 is a no-op for this call: it pushes nothing, its window slots and fill stay as they are,
+ *   and NONE of its inputs is read -- obs row, action, reward, done (the env keeps reporting 1 for an agent that has
+ *   left), next_obs row.  An active column does exactly what slhip_replay_add does for it, and the ring slots are handed
+ *   out by the same exclusive prefix sum of the push counts over the columns in index order: the ring's order is the
+ *   reference's.
+ * The window stays ONE ring over t mod n for all columns: a column is only ever inactive after a step of its own with
+ * done, which set its fill to 0, so the fill slots behind *head that it reads once it is back are its own contiguous
+ * steps.  capacity >= B * (n + 1) with B the columns.  Still two launches: the plan records "inactive" in plan_code, and
+ * the copy kernel's workgroup of such a column leaves before it loads anything else.  The carried state (who is active,
+ * num_resets) is not moved here: slhip_rollout_record_multi is its one implementation. */
+int slhip_replay_add_masked(const sl_replay *buf, const void *obs, const int32_t *actions, const void *rewards,
+                            const uint8_t *done, const void *next_obs, const uint8_t *active, void *stream);
 
 /* k distinct indices in [0, N), N = min(*idx, capacity) read on the device, by Floyd's algorithm; 1 <= k <=
  * SL_REPLAY_MAX_K.  For i = 0 .. k-1: j = N - k + i; z_i = the splitmix64 finalizer of seed + G * (counter * 0x100000001B3
@@ -840,6 +859,13 @@ int slhip_replay_gather(const sl_replay *buf, const long long *index, int k, voi
  * that holds envs [lo, lo + B) of a larger batch passes seed + G * lo. */
 int slhip_sample_actions_eps(const float *qvals, int B, int n_actions, double epsilon, unsigned long long seed,
                              unsigned long long counter, int32_t *actions, void *stream);
+
+/* slhip_sample_actions_eps with a mask: rows with active[e] == 0 get action 0 and their Q-values are not read (NaN rows
+ * included); every other row gets exactly the draw of slhip_sample_actions_eps for row e.  active: uint8 [B] (NULL: all
+ * active).  For a multi-agent batch the rows are the columns e * n_agents + a, and a caller that holds envs [lo, hi) of a
+ * larger run passes seed + G * lo * n_agents (the rule of slhip_sample_actions_masked). */
+int slhip_sample_actions_eps_masked(const float *qvals, const uint8_t *active, int B, int n_actions, double epsilon,
+                                    unsigned long long seed, unsigned long long counter, int32_t *actions, void *stream);
 
 /* ---- multi-agent PPO training batches: the masked rollout window (additive to ABI 13: seven new symbols and one new
  * struct, nothing existing changes, so SL_ABI_VERSION stays where it is) ------------------------------------------------

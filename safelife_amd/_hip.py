@@ -33,6 +33,7 @@ EXPORTS = (
     "slhip_render_boards", "slhip_env_render",
     "slhip_rollout_record", "slhip_training_batch",
     "slhip_replay_add", "slhip_replay_sample", "slhip_replay_gather", "slhip_sample_actions_eps",
+    "slhip_replay_add_masked", "slhip_sample_actions_eps_masked",
     "slhip_sample_actions_masked", "slhip_rollout_record_multi", "slhip_training_batch_multi",
     "slhip_rollout_compact_chunks", "slhip_rollout_compact", "slhip_rollout_gather",
 )
@@ -269,6 +270,9 @@ def lib():
         L.slhip_replay_sample.argtypes = [C.POINTER(Replay), C.c_int, C.c_ulonglong, C.c_ulonglong, _p, _p]
         L.slhip_replay_gather.argtypes = [C.POINTER(Replay), _p, C.c_int, _p, _p, C.c_int, _p, _p, _p, _p]
         L.slhip_sample_actions_eps.argtypes = [_p, C.c_int, C.c_int, C.c_double, C.c_ulonglong, C.c_ulonglong, _p, _p]
+        L.slhip_replay_add_masked.argtypes = [C.POINTER(Replay), _p, _p, _p, _p, _p, _p, _p]
+        L.slhip_sample_actions_eps_masked.argtypes = [_p, _p, C.c_int, C.c_int, C.c_double, C.c_ulonglong, C.c_ulonglong,
+                                                      _p, _p]
         L.slhip_sample_actions_masked.argtypes = [_p, _p, C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, _p, _p]
         L.slhip_rollout_record_multi.argtypes = [C.POINTER(RolloutMulti), C.c_int, _p, _p, C.c_int, _p, _p, _p, _p, _p, _p]
         L.slhip_training_batch_multi.argtypes = [C.POINTER(RolloutMulti), _p, C.c_double, C.c_double, _p, _p, _p, _p]

@@ -1774,14 +1774,19 @@ static int check_replay(const sl_replay *buf) {
     return SL_OK;
 }
 
-int slhip_replay_add(const sl_replay *buf, const void *obs, const int32_t *actions, const void *rewards,
-                     const uint8_t *done, const void *next_obs, void *stream) {
+int slhip_replay_add_masked(const sl_replay *buf, const void *obs, const int32_t *actions, const void *rewards,
+                            const uint8_t *done, const void *next_obs, const uint8_t *active, void *stream) {
     if (int rc = check_replay(buf)) return rc;
     if (!buf->win_obs || !buf->win_action || !buf->win_reward || !buf->fill || !buf->head || !buf->plan_base || !buf->plan_code)
         return fail(SL_E_ARG, "replay_add: null window / workspace pointer");
     if (!obs || !actions || !rewards || !done || !next_obs) return fail(SL_E_ARG, "replay_add: null pointer");
-    const hipError_t err = sl::launch_replay_add(*buf, obs, actions, rewards, done, next_obs, (hipStream_t)stream);
+    const hipError_t err = sl::launch_replay_add(*buf, obs, actions, rewards, done, next_obs, active, (hipStream_t)stream);
     return err == hipSuccess ? SL_OK : hip_fail(err, "replay_add launch");
+}
+
+int slhip_replay_add(const sl_replay *buf, const void *obs, const int32_t *actions, const void *rewards,
+                     const uint8_t *done, const void *next_obs, void *stream) {
+    return slhip_replay_add_masked(buf, obs, actions, rewards, done, next_obs, nullptr, stream);
 }
 
 int slhip_replay_sample(const sl_replay *buf, int k, unsigned long long seed, unsigned long long counter,
@@ -1804,14 +1809,20 @@ int slhip_replay_gather(const sl_replay *buf, const long long *index, int k, voi
     return err == hipSuccess ? SL_OK : hip_fail(err, "replay_gather launch");
 }
 
-int slhip_sample_actions_eps(const float *qvals, int B, int n_actions, double epsilon, unsigned long long seed,
-                             unsigned long long counter, int32_t *actions, void *stream) {
+int slhip_sample_actions_eps_masked(const float *qvals, const uint8_t *active, int B, int n_actions, double epsilon,
+                                    unsigned long long seed, unsigned long long counter, int32_t *actions, void *stream) {
     if (B < 0 || n_actions < 1) return fail(SL_E_ARG, "sample_actions_eps: B must be >= 0 and n_actions >= 1");
     if (!(epsilon == epsilon)) return fail(SL_E_ARG, "sample_actions_eps: epsilon is NaN");
     if (B == 0) return SL_OK;
     if (!qvals || !actions) return fail(SL_E_ARG, "sample_actions_eps: null pointer");
-    const hipError_t err = sl::launch_sample_actions_eps(qvals, B, n_actions, epsilon, seed, counter, actions, (hipStream_t)stream);
+    const hipError_t err = sl::launch_sample_actions_eps(qvals, active, B, n_actions, epsilon, seed, counter, actions,
+                                                         (hipStream_t)stream);
     return err == hipSuccess ? SL_OK : hip_fail(err, "sample_actions_eps launch");
+}
+
+int slhip_sample_actions_eps(const float *qvals, int B, int n_actions, double epsilon, unsigned long long seed,
+                             unsigned long long counter, int32_t *actions, void *stream) {
+    return slhip_sample_actions_eps_masked(qvals, nullptr, B, n_actions, epsilon, seed, counter, actions, stream);
 }
 
 int slhip_obs_to_policy(const uint32_t *view, int B, int vh, int vw, const int32_t *channels, int C, void *out,

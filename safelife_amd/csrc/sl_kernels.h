@@ -97,16 +97,18 @@ hipError_t launch_rollout_gather(const sl_rollout_multi &buf, const long long *r
                                  const float *advantages, const void *obs, long long obs_bytes, void *obs_out,
                                  long long *actions_out, float *action_prob_out, float *returns_out, float *advantages_out,
                                  float *values_out, hipStream_t stream);
-// sl_replay.hip : DQN's n-step window and replay ring, its sampler and gather, the epsilon-greedy draw
+// sl_replay.hip : DQN's n-step window and replay ring, its sampler and gather, the epsilon-greedy draw (active null: every
+// column / row takes part)
 hipError_t launch_replay_add(const sl_replay &buf, const void *obs, const int32_t *actions, const void *rewards,
-                             const uint8_t *done, const void *next_obs, hipStream_t stream);
+                             const uint8_t *done, const void *next_obs, const uint8_t *active, hipStream_t stream);
 hipError_t launch_replay_sample(const sl_replay &buf, int k, unsigned long long seed, unsigned long long counter,
                                 long long *out_index, hipStream_t stream);
 hipError_t launch_replay_gather(const sl_replay &buf, const long long *index, int k, void *obs_out, void *next_obs_out,
                                 int obs_float32, long long *action_out, float *reward_out, float *done_out,
                                 hipStream_t stream);
-hipError_t launch_sample_actions_eps(const float *qvals, int B, int A, double epsilon, unsigned long long seed,
-                                     unsigned long long counter, int32_t *actions, hipStream_t stream);
+hipError_t launch_sample_actions_eps(const float *qvals, const uint8_t *active, int B, int A, double epsilon,
+                                     unsigned long long seed, unsigned long long counter, int32_t *actions,
+                                     hipStream_t stream);
 // envs [e_first, e_first + e_count) of the batch; actions / reward_t / done_t are indexed [t * tstride + e]
 // with the env's index in the whole batch
 // (sl_aql.hip dispatches the same kernel from queues of the library's own: PreparedStep below)

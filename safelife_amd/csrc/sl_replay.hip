@@ -13,6 +13,12 @@
 // back, adds r * gamma^k to its float64 reward (product, then sum: contraction is off), and writes action / reward /
 // done of the pushes that come from its slot.
 //
+// slhip_replay_add_masked is the same two launches with one more input, active [B] (null: everybody), for envs with
+// several agents: B is then envs * n_agents columns, and an agent that has left its level sits out until the env reloads.
+// The plan reads active[b] FIRST: an inactive column counts no push, keeps its fill, and gets PLAN_INACTIVE as its plan
+// code -- its done flag is not looked at (the env keeps reporting 1 for an agent that is gone).  The copy kernel's
+// workgroup of such a column reads its plan code and leaves: no row, action, reward or window slot of it is touched.
+//
 // The window is a ring over t mod n shared by all envs, so slot *head (where this step goes) is also the slot of the
 // step n steps back: every lane reads its piece of the old row before it writes the new one to the same address.
 #include "sl_kernels.h"
@@ -25,8 +31,11 @@ namespace {
 
 constexpr int PLAN_THREADS = 1024;
 constexpr int ROW_THREADS = 256;
+constexpr int PLAN_DONE = 1 << 8;           // plan_code: fill before the step | PLAN_DONE | PLAN_INACTIVE
+constexpr int PLAN_INACTIVE = 1 << 9;
 
-__global__ __launch_bounds__(PLAN_THREADS) void k_replay_plan(sl_replay buf, const uint8_t *__restrict__ done) {
+__global__ __launch_bounds__(PLAN_THREADS) void k_replay_plan(sl_replay buf, const uint8_t *__restrict__ done,
+                                                              const uint8_t *__restrict__ active) {
     __shared__ int wave_sum[PLAN_THREADS / 64];
     const int tid = threadIdx.x;
     const int B = buf.B, n = buf.n;
@@ -40,12 +49,16 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_replay_plan(sl_replay buf, con
         const int b = b0 + tid;
         int cnt = 0;
         if (b < B) {
-            const int f = min(max(buf.fill[b], 0), n);
-            const int d = done[b] != 0;
-            const int fn = min(f + 1, n);
-            cnt = (f == n ? 1 : 0) + (d ? fn : 0);
-            buf.fill[b] = d ? 0 : fn;
-            buf.plan_code[b] = f | (d << 8);
+            if (active && active[b] == 0) {
+                buf.plan_code[b] = PLAN_INACTIVE;       // pushes nothing; fill[b] stays, done[b] is not read
+            } else {
+                const int f = min(max(buf.fill[b], 0), n);
+                const bool d = done[b] != 0;
+                const int fn = min(f + 1, n);
+                cnt = (f == n ? 1 : 0) + (d ? fn : 0);
+                buf.fill[b] = d ? 0 : fn;
+                buf.plan_code[b] = f | (d ? PLAN_DONE : 0);
+            }
         }
         int total;
         const int before = block_exclusive_scan<PLAN_THREADS>(cnt, wave_sum, total);
@@ -70,8 +83,9 @@ __global__ __launch_bounds__(ROW_THREADS) void k_replay_copy(sl_replay buf, cons
     const int B = buf.B, n = buf.n;
     const long long cap = buf.capacity;
     const int code = buf.plan_code[b];
+    if (code & PLAN_INACTIVE) return;                   // before anything of the column is loaded
     const int fill_old = code & 0xff;
-    const bool done = (code >> 8) != 0;
+    const bool done = (code & PLAN_DONE) != 0;
     const int head = *buf.head;                         // the plan has moved it on
     const int cur = head > 0 ? head - 1 : n - 1;        // the slot of this step
     const bool push = fill_old == n;                    // the window was full: the step n steps back leaves it
@@ -257,11 +271,16 @@ __global__ __launch_bounds__(ROW_THREADS) void k_replay_gather_f32(sl_replay buf
     }
 }
 
-__global__ __launch_bounds__(256) void k_sample_actions_eps(const float *__restrict__ qvals, int B, int A, double epsilon,
-                                                            unsigned long long seed, unsigned long long counter,
-                                                            int32_t *__restrict__ actions) {
+__global__ __launch_bounds__(256) void k_sample_actions_eps(const float *__restrict__ qvals,
+                                                            const uint8_t *__restrict__ active, int B, int A,
+                                                            double epsilon, unsigned long long seed,
+                                                            unsigned long long counter, int32_t *__restrict__ actions) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= B) return;
+    if (active && active[e] == 0) {                     // an agent that is gone: action 0, its Q-values are not read
+        actions[e] = 0;
+        return;
+    }
     const unsigned long long z = draw_hash(seed, counter, (unsigned long long)e);
     const float u = draw_uniform24(z);
     int a;
@@ -286,8 +305,8 @@ __global__ __launch_bounds__(256) void k_sample_actions_eps(const float *__restr
 }  // namespace
 
 hipError_t launch_replay_add(const sl_replay &buf, const void *obs, const int32_t *actions, const void *rewards,
-                             const uint8_t *done, const void *next_obs, hipStream_t stream) {
-    hipLaunchKernelGGL(k_replay_plan, dim3(1), dim3(PLAN_THREADS), 0, stream, buf, done);
+                             const uint8_t *done, const void *next_obs, const uint8_t *active, hipStream_t stream) {
+    hipLaunchKernelGGL(k_replay_plan, dim3(1), dim3(PLAN_THREADS), 0, stream, buf, done, active);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
     const dim3 grid((unsigned)buf.B), block(ROW_THREADS);
@@ -331,10 +350,11 @@ hipError_t launch_replay_gather(const sl_replay &buf, const long long *index, in
     return hipGetLastError();
 }
 
-hipError_t launch_sample_actions_eps(const float *qvals, int B, int A, double epsilon, unsigned long long seed,
-                                     unsigned long long counter, int32_t *actions, hipStream_t stream) {
-    hipLaunchKernelGGL(k_sample_actions_eps, dim3((B + 255) / 256), dim3(256), 0, stream, qvals, B, A, epsilon, seed, counter,
-                       actions);
+hipError_t launch_sample_actions_eps(const float *qvals, const uint8_t *active, int B, int A, double epsilon,
+                                     unsigned long long seed, unsigned long long counter, int32_t *actions,
+                                     hipStream_t stream) {
+    hipLaunchKernelGGL(k_sample_actions_eps, dim3((B + 255) / 256), dim3(256), 0, stream, qvals, active, B, A, epsilon, seed,
+                       counter, actions);
     return hipGetLastError();
 }
 

@@ -10,7 +10,8 @@ convolves (``policy_layout``), actions are sampled on the device, finished envs 
 kernel (``auto_reset``), and nothing visits the host.
 
 What carries over from the reference, per step and per agent (= per env for ``VectorRunner``, ``DQNRunner`` and
-``PipelinedRunner``; ``MultiAgentRunner`` at the end of the file drives envs with several agents):
+``PipelinedRunner``; ``MultiAgentRunner`` and ``MultiAgentDQNRunner`` at the end of the file drive envs with several
+agents):
 ``obs, actions, rewards, done, next_obs, agent_ids, policies, values`` with the reference's meaning --
 ``done`` describes the step that was just taken, ``next_obs`` of a finished env is already the first
 observation of its next episode, and an agent id changes when its env resets (``(env index, resets so far)``
@@ -22,6 +23,7 @@ import collections
 StepResult = collections.namedtuple("StepResult", "obs actions rewards done next_obs agent_ids policies values")
 DQNStep = collections.namedtuple("DQNStep", "obs actions rewards done next_obs agent_ids")
 MultiAgentStep = collections.namedtuple("MultiAgentStep", StepResult._fields + ("active",))
+MultiAgentDQNStep = collections.namedtuple("MultiAgentDQNStep", DQNStep._fields + ("active",))
 
 _SPLITMIX_G = 0x9E3779B97F4A7C15        # the increment of the draw kernel's splitmix64 (slhip_sample_actions)
 
@@ -438,3 +440,109 @@ class MultiAgentRunner(object):
         with torch.no_grad():
             final_values = self.policy(self._model_in(step.next_obs))[0]
         return buf.finish(final_values.reshape(env.num_envs, env.n_agents), gamma, lmda, gather_obs=gather_obs, dense=dense)
+
+
+class MultiAgentDQNRunner(object):
+    """``DQNRunner`` for envs with SEVERAL agents: the reference's DQN (training/dqn.py:93-108, 177-191) over
+    ``obs_for_envs`` / ``act_on_envs`` (training/base_algo.py:152-244), without the host.  A finished agent gets no action
+    (the env is handed 0 for it) and no row in the replay buffer until its env reloads, which happens -- inside the step
+    kernel -- once ALL its agents are done.  Who is active (``active`` uint8 ``[B, A]``, ``num_resets`` int64 ``[B]``) is
+    kept on the device and moved on once per step by ``slhip_rollout_record_multi``, through a one-step
+    ``MultiAgentRolloutBuffer`` as in ``MultiAgentRunner``: there is one implementation of that rule.
+
+    ``q_model`` is called on ALL ``B * A`` rows and what it returns for inactive rows is ignored (NaN included): a
+    compacted input would need the active count on the host every step.  The action of agent ``a`` of env ``e`` at step
+    ``c`` is the draw of ``slhip_sample_actions_eps`` for row ``(env_offset + e) * A + a`` under ``(seed, c)``.
+
+    Parameters: ``env`` a ``SafeLifeMultiAgentVectorEnv(policy_layout=..., auto_reset=True)``;
+    ``q_model(obs [B*A, C, vw, vh]) -> qvals [B*A, n_actions]`` on the device; ``cast_obs``: True hands the model float32
+    (dqn.py:97), False the env's tensor as it is.
+    """
+
+    _StateStep = collections.namedtuple("_StateStep", "obs actions rewards done policies values")
+
+    def __init__(self, env, q_model, seed=0, cast_obs=True):
+        import torch
+        from . import _hip
+        from .rollout import MultiAgentRolloutBuffer
+        self.torch, self._hip = torch, _hip
+        if getattr(env, "n_agents", None) is None or env.policy_tensor is None:
+            raise ValueError("MultiAgentDQNRunner needs SafeLifeMultiAgentVectorEnv(policy_layout=...)")
+        if not env.base.auto_reset:
+            raise ValueError("MultiAgentDQNRunner needs auto_reset=True (an env reloads inside the step kernel once all "
+                             "its agents are done)")
+        self.env, self.q_model, self.cast_obs = env, q_model, cast_obs
+        B, A = env.num_envs, env.n_agents
+        self.seed = (int(seed) + _SPLITMIX_G * int(env.base.env_offset) * A) & (2 ** 64 - 1)
+        self.env_ids = torch.arange(B, device=env.device, dtype=torch.int64)
+        self.actions = torch.zeros((B, A), dtype=torch.int32, device=env.device)
+        #: active agent steps taken so far, as a device tensor
+        self.num_agent_steps = torch.zeros(1, dtype=torch.int64, device=env.device)
+        self.num_steps = 0          # env steps * envs, as dqn.py:191 counts
+        self.draws = 0              # the draw counter: steps taken
+        reward = env.shaped_reward if env.shaped_reward is not None else env.reward
+        # the carried state and the one kernel that moves it on (the one-step window itself is not used)
+        self._state = MultiAgentRolloutBuffer(B, A, 1, None, None, reward.dtype, env.device)
+        self._no_values = torch.zeros(B * A, dtype=torch.float32, device=env.device)
+        self._started = False
+        self._lib = _hip.lib()
+
+    @property
+    def active(self):
+        """uint8 [B, A]: who takes part in the NEXT step."""
+        return self._state.active_now
+
+    @property
+    def num_resets(self):
+        """int64 [B]: reloads of every env so far (``env.num_resets`` of the reference)."""
+        return self._state.num_resets
+
+    def take_one_step(self, epsilon):
+        """``obs actions rewards done next_obs agent_ids active`` of one step of every env, the fields shaped
+        ``[B, A, ...]``: ``active`` uint8 ``[B, A]`` says who took part -- the rows of the others are to be ignored (their
+        action is 0, their ``done`` stays 1 as the env reports it).  ``obs`` is an own copy, ``actions`` an own int32
+        copy, ``rewards`` is ``env.shaped_reward`` when the env has ``wrappers=``, else ``env.reward``; ``next_obs`` is the
+        env's tensor, valid until the next step; ``agent_ids`` is ``(env index [B], resets so far [B])``, the agent being
+        the column."""
+        torch, env, _hip = self.torch, self.env, self._hip
+        if not self._started:
+            env.reset()
+            self._started = True
+        B, A = env.num_envs, env.n_agents
+        obs = env.policy_tensor
+        with torch.no_grad():
+            qvals = self.q_model(_model_in(obs.view((-1,) + tuple(obs.shape[2:])), self.cast_obs))
+        if qvals.dtype != torch.float32 or not qvals.is_contiguous():
+            qvals = qvals.to(torch.float32).contiguous()
+        if qvals.dim() != 2 or qvals.shape[0] != B * A:
+            raise ValueError("q_model must return [num_envs * n_agents, n_actions]")
+        state = self._state
+        active = state.active_now.clone()
+        agent_ids = (self.env_ids, state.num_resets.clone())
+        rc = self._lib.slhip_sample_actions_eps_masked(_hip.ptr(qvals), _hip.ptr(active), B * A, qvals.shape[1],
+                                                       float(epsilon), self.seed, self.draws, _hip.ptr(self.actions),
+                                                       _hip.current_stream_ptr())
+        if rc:
+            _hip.check(rc)
+        self.draws += 1
+        kept = obs.clone()
+        env.step(self.actions)
+        rewards = (env.shaped_reward if env.shaped_reward is not None else env.reward).clone()
+        done = env.done.to(torch.bool)
+        self.num_agent_steps += active.sum()
+        step = MultiAgentDQNStep(kept, self.actions.clone(), rewards, done, env.policy_tensor, agent_ids, active)
+        # active / num_resets move on (the Q-values stand in for the probabilities of the window nobody reads)
+        state.record(0, self._StateStep(None, step.actions, rewards, done, qvals, self._no_values))
+        return step
+
+    def collect(self, steps, epsilon, replay):
+        """``steps`` steps of every env, each added to ``replay`` (a ``MultiAgentReplayBuffer``); ``epsilon`` is a number
+        or a function of ``num_steps`` (the reference's ``epsilon_schedule``).  ``num_steps`` counts env steps * envs,
+        ``num_agent_steps`` the active agent steps.  Returns the last step."""
+        step = None
+        for _ in range(int(steps)):
+            eps = epsilon(self.num_steps) if callable(epsilon) else epsilon
+            step = self.take_one_step(float(eps))
+            replay.add(step)
+            self.num_steps += self.env.num_envs
+        return step
