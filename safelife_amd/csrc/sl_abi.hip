@@ -317,7 +317,7 @@ int slhip_life_occupancy(const uint16_t *in, int32_t *counts, int B, int H, int 
     // reference is called with.  Other shapes count in global memory (k_advance_generic): the LDS-counter kernel of
     // the side-effect pass (k_occupancy_generic) measured 5 % faster on 13x17 and 17 % slower on 33x64 boards
     // (profiles/occupancy_generic_bench.json), so it is not taken here.  SL_LIFE_OCCUPANCY_LDS is the timing-only
-    // build that measurement compares (tools/occupancy_generic_bench.py), like SL_OCC_NODRAW in sl_rowlane.hip.
+    // build that measurement compares (tools/occupancy_generic_bench.py).
     const hipStream_t st = (hipStream_t)stream;
     const size_t board_counts = (size_t)H * W * 8;
     hipError_t err;

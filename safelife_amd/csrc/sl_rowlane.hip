@@ -10,7 +10,8 @@
 //   * HBM -> LDS: the workgroup's boards are one contiguous, 16-byte aligned span moved by the
 //     global_load_lds DMA (no VGPR staging); LDS -> HBM by lane-linear 16-byte stores.  The flat LDS
 //     image is what the agent's action, the exit repaint, the on-device reset and the observation
-//     epilogue work on; rows wider than 32 cells are stored bank-swizzled (Geom::cell);
+//     epilogue work on; rows that are a whole number of 16-byte chunks are read and written as chunks, bank-swizzled
+//     where the chunk count is even (Geom::cell), the other rows as aligned dwords;
 //   * the 3x3 neighbourhood reduction is the commutative merge of sl_device.h in SWAR form: OR ("seen
 //     once"), majority ("seen twice") and integer add (alive count) on whole registers, bitop3 for every
 //     three-input function;
@@ -21,7 +22,12 @@
 //   * the score sum(points_table * alive_counts) is a per-cell byte gather from a table indexed by the
 //     cell's relevant bits and the goal colour (slhip_env_prepare builds it);
 //   * the training wrappers of env_wrappers.py run in the WRAP variants (leader lane, float64);
-//   * the only workgroup barriers are the two around the HBM <-> LDS moves.
+//   * workgroup barriers of a fused single step: the load barrier behind the HBM -> LDS moves; an LDS-only
+//     barrier behind the agent's move where the leaders take its cells from the image (the plain single-step kernels of
+//     the narrow shapes; the other kernels hand the move over in a mailbox or, inside a step loop, behind a barrier of
+//     its own); one in front of the leaders' section (scores in the mailbox) and one behind it, in front of the
+//     LDS -> HBM stores, where the rows also carry out what the leaders asked for (queue a board, load a level).
+//     advance_board and life_occupancy have the two around their moves, or none (one wavefront per workgroup).
 //
 // Reference behaviour restated: advance_board.c:34-125 (CA step), :153-189 (occupancy), :217-300
 // (actions), safelife_env.py:148-218 + safelife_game.py:505-552,684-719,746-761 (step / reset glue),
@@ -34,20 +40,6 @@
 
 #include "sl_kernels.h"
 #include "sl_planes.h"
-
-// A/B knobs of the span moves (cache policy of the LDS DMA loads, flavour of the span stores)
-#ifndef SL_LOAD_AUX
-#define SL_LOAD_AUX 0
-#endif
-#ifndef SL_STORE
-#define SL_STORE 1   /* 0 plain, 1 non-temporal, 2 sc1 (write-through), 3 sc0 sc1.  Round 3, two-slice C3 step: 8.2-8.3 us
-                        plain, 7.9 non-temporal, 7.95-8.0 either write-through form.  What the flavours change is the
-                        kernel BOUNDARY: in-kernel clocks (tools/trace_overlap.py) put 2.0-2.5 us between a slice's last
-                        acknowledged store and the first wave of its next launch, of which ~0.9 us are the write-back
-                        of the 5.6 MB the launch left dirty in L2; streaming lines leave earlier.  Non-temporal stores
-                        keep the ordinary coherence rules.  The write-through forms produced WRONG boards now and then
-                        under concurrent launches in round 2 (64x64 spawner levels, ~1 run in 3) and stay a knob. */
-#endif
 
 namespace sl {
 namespace rl {
@@ -145,15 +137,10 @@ struct Geom {
     static_assert(G >= 1, "H must be <= 64");
     static_assert(WS <= 32 && W >= 4 && H >= 4, "row-per-lane path: 4 <= W <= 64, H >= 4");
     static constexpr int WAVES_PER_SIMD = WS <= 16 ? 4 : 2;   // VGPR budget: 128 / 256 registers
-    // fused step, LEAN variants of the narrow shapes: a fifth wavefront that holds no rows leads the workgroup
-    // (four workgroups per CU -> five waves per SIMD -> 96 registers)
-    // -- measured and switched off: the wave's lifetime drops (4.7 -> 4.57 us at 4096 envs) but the two-slice step does
-    //    not move (8.26 us) and the one-launch step loses (9.6 -> 10.9 us: twenty waves per CU spread unevenly over
-    //    the SIMDs)
-#ifndef SL_LEADX
-#define SL_LEADX 0              /* A/B knob: 1 = the LEAN variants of the 25 / 26-cell shapes get a fifth, row-less leader wave */
-#endif
-    static constexpr bool LEADX_OK = SL_LEADX && (W == 25 || W == 26);
+    // (round 3, measured and dropped: a fifth, row-less wavefront that leads the workgroup in the LEAN variants of the
+    //  25 / 26-cell shapes -- four workgroups per CU, five waves per SIMD, 96 registers.  The wave's lifetime drops,
+    //  4.7 -> 4.57 us at 4096 envs, but the two-slice step does not move (8.26 us) and the one-launch step loses,
+    //  9.6 -> 10.9 us: twenty waves per CU spread unevenly over the SIMDs)
     static constexpr int NL = G * GL;                      // lanes in use
     static constexpr int NB = WAVES * G;                   // boards per workgroup
     static_assert((NB * HW) % 8 == 0, "workgroup span must be a multiple of 16 bytes");
@@ -197,11 +184,8 @@ struct Geom {
     // (y >> 2) & 3, 16 and 48 cells (y >> 3) & 1; an odd chunk count (8, 24, 40 cells) sweeps the banks by itself.
     // (The key has a period of sixteen rows and the DMA works on rows of the whole span: H must be a multiple of 16
     //  wherever there is a key.)
-#ifndef SL_SWZ_ALL
-#define SL_SWZ_ALL 1            /* A/B knob: 0 = only 64-cell rows are chunked and swizzled (rounds 1-3) */
-#endif
     static constexpr int CH = W / 8;
-    static constexpr bool SWZ = W == 64 || (SL_SWZ_ALL && W % 8 == 0 && (W == 8 || W == 24 || W == 40 || H % 16 == 0));
+    static constexpr bool SWZ = W == 64 || (W % 8 == 0 && (W == 8 || W == 24 || W == 40 || H % 16 == 0));
     static constexpr int KM = !SWZ ? 0 : W == 64 ? 7 : W == 32 ? 3 : (W == 16 || W == 48) ? 1 : 0;
     static constexpr int KS = W == 64 ? 1 : W == 32 ? 2 : 3;
     static_assert(KM == 0 || H % 16 == 0, "swizzled images: the key's period is sixteen rows");
@@ -209,16 +193,10 @@ struct Geom {
     // (the image starts 16-byte aligned, a board and a row are an even number of cells), so the rows are read and
     // written as W / 2 aligned dwords -- half the LDS instructions of the cell-by-cell form for the same number of
     // vector instructions (one v_perm per word of the split layout either way).
-#ifndef SL_ROW_DWORDS
-#define SL_ROW_DWORDS 1         /* A/B knob: 0 = such rows cell by cell (rounds 1-3) */
-#endif
-    static constexpr bool DW = SL_ROW_DWORDS && !SWZ && (W & 1) == 0;
+    static constexpr bool DW = !SWZ && (W & 1) == 0;
     // Odd rows, READS only (a row's first or last cell shares its dword with a neighbouring row, which another lane
     // writes): the WS + 1 aligned dwords that cover the row, shifted into place per lane.
-#ifndef SL_ROW_ODD_DWORDS
-#define SL_ROW_ODD_DWORDS 1     /* A/B knob: 0 = odd rows are read cell by cell (rounds 1-3) */
-#endif
-    static constexpr bool ODW = SL_ROW_ODD_DWORDS && !SWZ && (W & 1) == 1;
+    static constexpr bool ODW = !SWZ && (W & 1) == 1;
     static __device__ __forceinline__ int key(int y) { return KM ? (y >> KS) & KM : 0; }
     static __device__ __forceinline__ int swz_chunk(int s) {           // LDS slot (16-byte chunk of the span) -> global chunk
         return KM ? s ^ key(s / CH) : s;
@@ -238,12 +216,12 @@ template <int H, int W>
 using RowWords = u32[Geom<H, W>::WS];
 
 // ---- flat LDS image  <->  row-per-lane registers ------------------------------------------------
-// Two 16-bit LDS reads per word (gfx950 has SRAM-ECC, so d16_hi loads do not preserve the other
-// half and cannot merge in place).  The reads are volatile only to stop the compiler from fusing
-// neighbouring cells into wide ds_read_b64 accesses that would be misaligned for odd row starts.
+// Every shape reads its rows in one of three aligned forms (rounds 1-3 read all but the 64-cell rows cell by cell: two
+// 16-bit LDS reads per word, since gfx950 has SRAM-ECC and d16_hi loads cannot merge in place).
 template <int H, int W>
 __device__ __forceinline__ void read_row(const unsigned char *region, int gb, int r, RowWords<H, W> &b) {
     using Gm = Geom<H, W>;
+    static_assert(Gm::SWZ || Gm::DW || Gm::ODW, "read_row: chunks, dwords or the odd rows' dwords");
     if (Gm::SWZ) {      // eight aligned 16-byte reads (chunk j sits at j ^ key), then one v_perm per word
         typedef const __attribute__((address_space(3))) u32x4 *lds_c128;
         lds_c128 row = (lds_c128)(region + Gm::PAD) + (gb * Gm::HW + r * W) / 8;
@@ -291,18 +269,7 @@ __device__ __forceinline__ void read_row(const unsigned char *region, int gb, in
             const u32 sel = ((k & 1) ? 0x0302u : 0x0100u) | ((((k + Gm::WS) & 1) ? 0x0706u : 0x0504u) << 16);
             b[k] = k == Gm::WS - 1 ? (x[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu : __builtin_amdgcn_perm(x[(k + Gm::WS) >> 1], x[k >> 1], sel);
         }
-        return;
     }
-    typedef const volatile __attribute__((address_space(3))) u16 *lds_cv16;
-    lds_cv16 c = (lds_cv16)(region + Gm::PAD) + gb * Gm::HW + r * W;
-    u32 lo[Gm::WS], hi[Gm::WS];
-#pragma unroll
-    for (int k = 0; k < Gm::WS; ++k) {
-        lo[k] = c[k];
-        hi[k] = (Gm::ODD && k == Gm::WS - 1) ? 0u : (u32)c[k + Gm::WS];
-    }
-#pragma unroll
-    for (int k = 0; k < Gm::WS; ++k) b[k] = lo[k] | (hi[k] << 16);
 }
 
 template <int H, int W>
@@ -337,11 +304,7 @@ __device__ __forceinline__ void write_row(unsigned char *region, int gb, int r, 
         }
         return;
     }
-#ifdef SL_EXP_WROW16
-    volatile u16 *c = (volatile u16 *)(region + Gm::PAD) + gb * Gm::HW + r * W;
-#else
     u16 *c = (u16 *)(region + Gm::PAD) + gb * Gm::HW + r * W;
-#endif
 #pragma unroll
     for (int k = 0; k < Gm::WS; ++k) {
         c[k] = (u16)n[k];
@@ -713,57 +676,39 @@ __device__ __forceinline__ U128 pcg_jump_cached(const Jump *__restrict__ table, 
 // wave loops ceil(busiest word / 2) times instead of once per cell and word, and the trips' chains are independent.
 // The loop is the longest serial stretch of a spawner board's step: 64x64 navigation, ~8 + ~8 flagged cells in the
 // busiest row's two words: 16 trips -> 4.
-#ifndef SL_DEAL_PAIRS
-#define SL_DEAL_PAIRS 2         /* cells of each word per trip (0: the words one after the other, a cell per trip; 4: no faster) */
-#endif
-#ifndef SL_STRIDE_DEAL
-#define SL_STRIDE_DEAL 1        /* A/B knob: 0 = the blocked deal for every step */
-#endif
-#ifndef SL_STRIDE_ROUNDS2
-#define SL_STRIDE_ROUNDS2 4     /* two boards per wave: rounds (of 32 draws per board) the round-by-round deal takes; a step
-                                   with more draws goes row by row (below) -- the blocked deal is not kept beside it: both
-                                   together cost the 25x25 step kernels the registers of their scratch-free build */
-#endif
+// (4 cells of each word per trip: no faster; the words one after the other, a cell per trip: the form of rounds 1-4)
+constexpr int DEAL_PAIRS = 2;           // cells of each word per trip
+// two boards per wave: rounds (of 32 draws per board) the round-by-round deal takes; a step with more draws goes row by
+// row (below) -- the blocked deal is not kept beside it: both together cost the 25x25 step kernels the registers of their
+// scratch-free build
+constexpr int STRIDE_ROUNDS2 = 4;
 template <int NW>
 __device__ __forceinline__ void deal_outcomes(const pl::Pl<NW> &elig, u64 R, pl::Pl<NW> &ok) {
-    if constexpr (SL_DEAL_PAIRS && NW <= 2) {
-        u32 t[NW], g[NW], r[NW];
-        t[0] = elig.w[0], g[0] = 0, r[0] = (u32)R;
-        if constexpr (NW == 2) {
-            t[1] = elig.w[1], g[1] = 0;
-            r[1] = (u32)(R >> __popc(t[0]));    // (popc <= 32; the window holds the lane's <= 64 outcomes)
-        }
-        u32 any = t[0];
-        if constexpr (NW == 2) any |= t[1];
-        while (any) {
-#pragma unroll
-            for (int i = 0; i < NW; ++i) {
-#pragma unroll
-                for (int k = 0; k < SL_DEAL_PAIRS; ++k) {
-                    const u32 bit = t[i] & (0u - t[i]);
-                    g[i] |= (0u - (r[i] & 1u)) & bit;
-                    r[i] >>= 1;
-                    t[i] ^= bit;
-                }
-            }
-            any = t[0];
-            if constexpr (NW == 2) any |= t[1];
-        }
-#pragma unroll
-        for (int i = 0; i < NW; ++i) ok.w[i] = g[i];
-    } else {
+    static_assert(NW <= 2, "a plane is one word, or two (64-cell rows)");
+    u32 t[NW], g[NW], r[NW];
+    t[0] = elig.w[0], g[0] = 0, r[0] = (u32)R;
+    if constexpr (NW == 2) {
+        t[1] = elig.w[1], g[1] = 0;
+        r[1] = (u32)(R >> __popc(t[0]));    // (popc <= 32; the window holds the lane's <= 64 outcomes)
+    }
+    u32 any = t[0];
+    if constexpr (NW == 2) any |= t[1];
+    while (any) {
 #pragma unroll
         for (int i = 0; i < NW; ++i) {
-            u32 todo = elig.w[i], got = 0;
-            while (todo) {
-                const u32 bit = todo & (0u - todo);
-                got |= (R & 1ull) ? bit : 0u;
-                R >>= 1;
-                todo ^= bit;
+#pragma unroll
+            for (int k = 0; k < DEAL_PAIRS; ++k) {
+                const u32 bit = t[i] & (0u - t[i]);
+                g[i] |= (0u - (r[i] & 1u)) & bit;
+                r[i] >>= 1;
+                t[i] ^= bit;
             }
-            ok.w[i] = got;
         }
+        any = t[0];
+        if constexpr (NW == 2) any |= t[1];
     }
+#pragma unroll
+    for (int i = 0; i < NW; ++i) ok.w[i] = g[i];
 }
 
 // (JC is a template parameter, not just a null pointer: the extra argument alone cost the fused step's spawner
@@ -791,7 +736,7 @@ __device__ pl::Pl<NW> resolve_draws_planes(const pl::Pl<NW> &elig, u64 *rng_lds,
     }
     const int excl = incl - mine - before;
     constexpr int MAXR = 8;             // rounds of the round-by-round deal (below)
-    const bool stride_now = Gm::G == 1 && SL_STRIDE_DEAL && total <= 64 * MAXR;        // (wave-uniform)
+    const bool stride_now = Gm::G == 1 && total <= 64 * MAXR;        // (wave-uniform)
     const U128 st = {rng_lds[4 * g + 0], rng_lds[4 * g + 1]}, inc = {rng_lds[4 * g + 2], rng_lds[4 * g + 3]};
     // two boards per wave: lanes 0-31 make the draws of board 0, lanes 32-63 those of board 1 (below), whatever
     // rows they hold
@@ -928,8 +873,8 @@ __device__ pl::Pl<NW> resolve_draws_planes(const pl::Pl<NW> &elig, u64 *rng_lds,
         // q (one c for both boards); the xor swizzles stay inside a half; a row's lane pulls its dwords from the
         // half of its OWN board.
         const int tmax = max(tot_q[0], tot_q[1]);
-        constexpr int MAXR2 = SL_STRIDE_ROUNDS2;     // (more rounds cost the 25x25 step kernels registers they do not have)
-        if (SL_STRIDE_DEAL && tmax <= 32 * MAXR2) {
+        constexpr int MAXR2 = STRIDE_ROUNDS2;     // (more rounds cost the 25x25 step kernels registers they do not have)
+        if (tmax <= 32 * MAXR2) {
             // the round-by-round deal on the two halves: lane j of half q makes draws j, j + 32, ... of board q -- a jump
             // by j + 1, then steps of 32 (the table's entry 32) -- and round r's outcomes are the compare's lane mask,
             // board 0's in its low dword, board 1's in its high one.  A 25x25 board with a spawner or two draws ~10
@@ -995,55 +940,6 @@ __device__ pl::Pl<NW> resolve_draws_planes(const pl::Pl<NW> &elig, u64 *rng_lds,
             wave_sync();
             return ok;
         }
-#if !SL_STRIDE_DEAL
-        if (tmax <= 32 * 32) {
-            const int lane = (int)__lane_id(), j = lane & 31;
-            const int need = (tmax + 31) >> 5;
-            const int log2c = need <= 1 ? 0 : 32 - __clz(need - 1);            // c = 2^log2c >= tmax / 32
-            const int total_w = wq ? tot_q[1] : tot_q[0];
-            const int first = j << log2c;
-            const int n_here = min(max(total_w - first, 0), 1 << log2c);
-            // (the threshold is the BOARD's: taken from a lane that holds one of its rows)
-            const u32 tl0 = __builtin_amdgcn_readlane((u32)thr, LaneMap<H, W>::first_lane(0) + 1);
-            const u32 th0 = __builtin_amdgcn_readlane((u32)(thr >> 32), LaneMap<H, W>::first_lane(0) + 1);
-            const u32 tl1 = __builtin_amdgcn_readlane((u32)thr, LaneMap<H, W>::first_lane(1) + 1);
-            const u32 th1 = __builtin_amdgcn_readlane((u32)(thr >> 32), LaneMap<H, W>::first_lane(1) + 1);
-            const u64 wthr = wq ? (((u64)th1 << 32) | tl1) : (((u64)th0 << 32) | tl0);
-            u32 bits = 0;
-            if (n_here > 0) {
-                U128 cur = pcg_jump_cached(jump, first, log2c, wst, winc, jc);
-                for (int i = 0; i < n_here; ++i) {
-                    cur = pcg_step(cur, winc);
-                    bits |= (pcg_output_u53(cur) < wthr ? 1u : 0u) << i;        // advance_board.c:115
-                }
-                if (first + n_here == total_w) {    // the lane that made the board's last draw holds its new state
-                    rng_lds[4 * wq + 0] = cur.hi;
-                    rng_lds[4 * wq + 1] = cur.lo;
-                }
-            }
-            const int per = 32 >> log2c;                                        // lanes per dword of outcomes
-            u32 v = bits << ((lane & (per - 1)) << log2c);
-            if (per > 1) v |= (u32)__builtin_amdgcn_ds_swizzle((int)v, 0x041F);      // xor 1
-            if (per > 2) v |= (u32)__builtin_amdgcn_ds_swizzle((int)v, 0x081F);      // xor 2
-            if (per > 4) v |= (u32)__builtin_amdgcn_ds_swizzle((int)v, 0x101F);      // xor 4
-            if (per > 8) v |= (u32)__builtin_amdgcn_ds_swizzle((int)v, 0x201F);      // xor 8
-            if (per > 16) v |= (u32)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);     // xor 16
-            // (round 5, measured and dropped: DPP quad permutes and row mirrors for the steps inside a row of sixteen
-            //  lanes -- bit exact, and no faster: the pass of C5 12.0-12.1 ms either way, C4's step 8.04-8.14)
-            // dword d of board q's outcome string sits in lanes [32 q + d per, 32 q + (d + 1) per)
-            const int w0 = excl >> 5, sh = excl & 31;
-            const int log2per = 5 - log2c;
-            const int base = 32 * g;
-            const u32 d0 = bperm(4 * (base + min(31, w0 << log2per)), v);
-            const u32 d1 = bperm(4 * (base + min(31, (w0 + 1) << log2per)), v);
-            const u32 d2 = bperm(4 * (base + min(31, (w0 + 2) << log2per)), v);
-            u64 R = (((u64)d1 << 32) | d0) >> sh;
-            if (sh) R |= (u64)d2 << (64 - sh);
-            deal_outcomes<NW>(elig, R, ok);
-            wave_sync();
-            return ok;
-        }
-#endif
     }
     if (mine > 0) {
         U128 cur = pcg_jump(jump, excl, st, inc);
@@ -1081,19 +977,10 @@ __device__ pl::Pl<NW> resolve_draws_planes(const pl::Pl<NW> &elig, u64 *rng_lds,
 // whether any cell of the wave changed -- the word form does not know and says yes.  `take`: the lane takes the
 // new row even if it is not `mine` (the halo copies of the word form compute their own rows).
 template <int H, int W>
-#ifndef SL_SPLIT_PLANES_MULTI
-#define SL_SPLIT_PLANES_MULTI 1 /* A/B knob: 0 = advance_board (n > 1) and life_occupancy keep rows of 32..48 cells in word form */
-#endif
-constexpr bool use_planes_multi() {                     // rows kept in plane form across steps
-    return (W + 1) / 2 + 2 <= 16 || W == 64 || (SL_SPLIT_PLANES_MULTI && W >= 32 && W < 64 && (W & 1) == 0);
-}
-template <int H, int W>
-constexpr bool use_planes() {       // single steps: also even rows of 32 to 60 cells (two words per plane, one per half;
-                                    // at 30 cells the word form is the faster one: 8.8 against 9.3-9.8 us per step)
-#ifndef SL_SPLIT_PLANES
-#define SL_SPLIT_PLANES 1       /* A/B knob: 0 = rows of 30 to 48 cells keep the word form of the CA (rounds 1-3) */
-#endif
-    return use_planes_multi<H, W>() || (SL_SPLIT_PLANES && W >= 32 && W < 64 && (W & 1) == 0);
+constexpr bool use_planes() {       // rows kept in plane form: up to 28 cells, and even rows of 32 to 64 cells (two words
+                                    // per plane, one per half; at 30 cells the word form is the faster one: 8.8 against
+                                    // 9.3-9.8 us per step.  Rounds 1-3 kept rows of 32 to 48 cells in word form)
+    return (W + 1) / 2 + 2 <= 16 || W == 64 || (W >= 32 && W < 64 && (W & 1) == 0);
 }
 
 template <int H, int W, bool SPAWN, bool COLFIRST>
@@ -1401,7 +1288,7 @@ __device__ __forceinline__ void dma_to_lds(const unsigned char *__restrict__ src
         const int s = c * 64 + lane;
         if (s < nv)
             __builtin_amdgcn_global_load_lds((glds_src_t)(src + (SWZ ? Perm::swz_chunk(s) : s) * 16),
-                                             (glds_dst_t)(dst + c * 1024), 16, 0, SL_LOAD_AUX);
+                                             (glds_dst_t)(dst + c * 1024), 16, 0, 0);
     }
 }
 
@@ -1414,17 +1301,13 @@ __device__ __forceinline__ void load_span(const u16 *__restrict__ src, unsigned 
     if (wave == 0 && lane < rem) ((u16 *)(region + Gm::PAD))[nv * 8 + lane] = src[nv * 8 + lane];
 }
 
-__device__ __forceinline__ void store16(u32x4 *p, u32x4 v) {
-#if SL_STORE == 1
-    __builtin_nontemporal_store(v, p);
-#elif SL_STORE == 2
-    asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-#elif SL_STORE == 3
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
-#else
-    *p = v;
-#endif
-}
+// Span stores are non-temporal.  (round 3, measured and dropped, two-slice C3 step: 8.2-8.3 us with plain stores, 7.9
+// non-temporal, 7.95-8.0 with either write-through form, sc1 or sc0 sc1.  What the flavours change is the kernel
+// BOUNDARY: in-kernel clocks (tools/trace_overlap.py) put 2.0-2.5 us between a slice's last acknowledged store and the
+// first wave of its next launch, of which ~0.9 us are the write-back of the 5.6 MB the launch left dirty in L2;
+// streaming lines leave earlier.  Non-temporal stores keep the ordinary coherence rules.  The write-through forms
+// produced WRONG boards now and then under concurrent launches in round 2 -- 64x64 spawner levels, ~1 run in 3.)
+__device__ __forceinline__ void store16(u32x4 *p, u32x4 v) { __builtin_nontemporal_store(v, p); }
 
 template <int H, int W>
 __device__ __forceinline__ void store_span(u16 *__restrict__ dst, const unsigned char *region, int nbb, int tid) {
@@ -1438,30 +1321,6 @@ __device__ __forceinline__ void store_span(u16 *__restrict__ dst, const unsigned
     for (int i = 0; i < NVI; ++i) {
         const int slot = tid + 64 * WAVES * i;
         if (slot < nv) store16(d + Gm::swz_chunk(slot), s[slot]);
-    }
-    const int rem = (bytes & 15) >> 1;
-    if (tid < rem) dst[nv * 8 + tid] = ((const u16 *)s)[nv * 8 + tid];
-}
-
-// The same for the fused step's boards, skipping the 16-byte chunks that lie entirely in boards whose mailbox says
-// "nothing changed" (the few cells the leaders touch in such a board they store themselves).
-template <int H, int W, class Box>
-__device__ __forceinline__ void store_span_dirty(u16 *__restrict__ dst, const unsigned char *region, int nbb, int tid,
-                                                 const Box *box) {
-    using Gm = Geom<H, W>;
-    static_assert(Gm::KM == 0, "row-major images only");
-    const int bytes = nbb * Gm::HW * 2;
-    const int nv = bytes >> 4;
-    u32x4 *d = (u32x4 *)dst;
-    const u32x4 *s = (const u32x4 *)(region + Gm::PAD);
-    constexpr int NVI = (Gm::SPAN / 16 + 64 * WAVES - 1) / (64 * WAVES);
-#pragma unroll
-    for (int i = 0; i < NVI; ++i) {
-        const int slot = tid + 64 * WAVES * i;
-        if (slot < nv) {
-            const int q0 = (slot * 8) / Gm::HW, q1 = min((slot * 8 + 7) / Gm::HW, nbb - 1);
-            if (box[q0].dirty | box[q1].dirty) store16(d + slot, s[slot]);
-        }
     }
     const int rem = (bytes & 15) >> 1;
     if (tid < rem) dst[nv * 8 + tid] = ((const u16 *)s)[nv * 8 + tid];
@@ -1573,7 +1432,7 @@ __global__ __launch_bounds__(64) void k_advance_small(const u16 *__restrict__ in
     const Consts cst = make_consts();
     const pl::PConsts pcst = pl::make_pconsts();
     wave_sync();
-    constexpr bool PLANES = use_planes_multi<H, W>();
+    constexpr bool PLANES = use_planes<H, W>();
     if constexpr (PLANES) {
         constexpr int NW = pl::PG<W>::NW;
         if (wave_n > 1) {               // many steps: one transposition at either end
@@ -1637,26 +1496,19 @@ struct OccGeom {
     static constexpr int CELL_DWORDS = SLOTS / PER_DWORD;
     static_assert(CELL_DWORDS >= 1, "at least one dword of counters per cell");
     static constexpr int PITCH = W * CELL_DWORDS + 1;                   // dwords per lane
-    // Round 5, measured and left off (SL_OCC_DIRECT): 64-cell rows WITHOUT counters in LDS -- the register counters
-    // (4-bit, bit-sliced) flushed every 15 counted steps straight into the zeroed int32 output as fire-and-forget global
-    // atomics, one per live cell, so that a wavefront needs 32 bytes of LDS instead of 16.6 KB and the kernel's 127
-    // registers, not its LDS, bound the wavefronts per SIMD (2 -> 4).  Bit exact, and twice as slow: the episode-end pass of
-    // C5 (2137 episodes) 23.3-23.9 ms against 12.5-12.7 -- 64 lanes x 64 addresses per atomic instruction are 64
-    // transactions at the L2, and the pass issues ~1e8 of them (profiles/round5_d_se_pass_variants.txt).
-#ifndef SL_OCC_DIRECT
-#define SL_OCC_DIRECT 0
-#endif
-    static constexpr bool DIRECT = SL_OCC_DIRECT && CB == 8 && use_planes_multi<H, W>();
+    // (round 5, measured and dropped: 64-cell rows WITHOUT counters in LDS -- the register counters flushed every 15
+    //  counted steps straight into the zeroed int32 output as fire-and-forget global atomics, one per live cell, so that
+    //  a wavefront needs 32 bytes of LDS instead of 16.6 KB and the kernel's 127 registers, not its LDS, bound the
+    //  wavefronts per SIMD, 2 -> 4.  Bit exact, and twice as slow: the episode-end pass of C5, 2137 episodes, 23.3-23.9
+    //  ms against 12.5-12.7 -- 64 lanes x 64 addresses per atomic instruction are 64 transactions at the L2, and the
+    //  pass issues ~1e8 of them: profiles/round5_d_se_pass_variants.txt)
     // 64-cell rows (two plane words): the register counters are transposed into byte lanes and added four cells at a
     // time, so a lane's counters are laid out [slot][plane word i][q] with byte j of that dword = cell 32 i + q + 8 j
-#ifndef SL_OCC_NIBBLE
-#define SL_OCC_NIBBLE 1         /* A/B knob: 0 = 64-cell rows walk their non-zero cells like the other shapes */
-#endif
-    static constexpr bool NIBBLE = SL_OCC_NIBBLE && CB == 8 && W == 64 && !DIRECT;
+    static constexpr bool NIBBLE = CB == 8 && W == 64;
     static constexpr int OFF_CNT = 0;
-    static constexpr int OFF_RNG = DIRECT ? 0 : 64 * PITCH * 4;         // G x 4 u64
+    static constexpr int OFF_RNG = 64 * PITCH * 4;        // G x 4 u64
     static constexpr int LDS_BYTES = OFF_RNG + Gm::G * 32;
-    static constexpr int FLUSH_EVERY = (CB == 8 && !DIRECT) ? 255 : 0x7FFFFFFF;
+    static constexpr int FLUSH_EVERY = CB == 8 ? 255 : 0x7FFFFFFF;
 };
 
 // counters of one lane's row -> its slice of the output (add: the output was zeroed), counters cleared.
@@ -1786,8 +1638,7 @@ __global__ __launch_bounds__(64) void k_occupancy_rowlane(const u16 *__restrict_
     u64 *rng_lds = (u64 *)(smem + Oc::OFF_RNG);
     int32_t *dst = counts + (size_t)e * counts_stride + ((size_t)r * W) * 8;    // this lane's row of the output
 
-    if (!Oc::DIRECT)
-        for (int i = 0; i < Oc::PITCH; ++i) cnt[i] = 0;
+    for (int i = 0; i < Oc::PITCH; ++i) cnt[i] = 0;
     if (lane < 4 * nbb) rng_lds[lane] = ((const u64 *)(rng + e0b))[lane];
     const double p = rowl ? (double)spawn_prob[e] : 0.0;
     // V_SHIFT: after a step the halo lanes take the new first / last row from the lanes that own them
@@ -1807,7 +1658,7 @@ __global__ __launch_bounds__(64) void k_occupancy_rowlane(const u16 *__restrict_
     // rows of up to 28 cells, or 64: the row stays in bit-plane form for all the steps (sl_planes.h) -- one
     // transposition at the start, the CA on whole rows, and the counting visits only the cells that ARE alive
     // (a handful per row) instead of every cell position
-    constexpr bool PLANES = use_planes_multi<H, W>();
+    constexpr bool PLANES = use_planes<H, W>();
     constexpr int NW = pl::PG<PLANES ? W : 8>::NW;
     pl::PState<NW> st;
     const pl::VCtx<Gm::VERT> vctx = {lm.up, lm.dn, 4 * partner};
@@ -1871,13 +1722,12 @@ __global__ __launch_bounds__(64) void k_occupancy_rowlane(const u16 *__restrict_
                     // the cell's column (split two-word planes: word i holds cells i WS .. from bit 1 on)
                     const int x = pl::PG<PLANES ? W : 8>::SPLIT ? i * WS + pos - 1
                                                                   : NW == 2 ? 32 * i + pos : (pos < 16 ? pos - 1 : pos - 17 + WS);
-                    if (Oc::DIRECT)     // straight into the (zeroed) output: counts[y, x, colour of the slot]
-                        __hip_atomic_fetch_add(dst + x * 8 + ((inv >> (3 * sl)) & 7u), (int32_t)val, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_AGENT);
-                    else
-                        __hip_atomic_fetch_add(cnt + x * Oc::CELL_DWORDS + sl / Oc::PER_DWORD,
-                                               val << (Oc::CB * (sl % Oc::PER_DWORD)), __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    // (dst and inv stay captured, as the dropped straight-to-output form had them: the closure's layout
+                    //  decides this kernel's register allocation, and its instructions are to stay as they are)
+                    (void)dst, (void)inv;
+                    __hip_atomic_fetch_add(cnt + x * Oc::CELL_DWORDS + sl / Oc::PER_DWORD,
+                                           val << (Oc::CB * (sl % Oc::PER_DWORD)), __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_WAVEFRONT);
                 }
 #pragma unroll
                 for (int k = 0; k < MINI_BITS; ++k) mini[sl][k][i] = 0;
@@ -1888,11 +1738,7 @@ __global__ __launch_bounds__(64) void k_occupancy_rowlane(const u16 *__restrict_
         if constexpr (PLANES) {
             const u32 realm = live && going ? vreg(pl::PG<W>::REAL) : 0u;
             pl::planes_step<W, Gm::VERT, true>(st, vctx, realm, [&](const pl::Pl<NW> &elig) {
-#ifdef SL_OCC_NODRAW
-                return elig;
-#else
                 return resolve_draws_planes<H, W, NW, true>(elig, rng_lds, rowl ? g : 0, p, jump, &jcache);
-#endif
             });
         } else {
             const bool changed = ca_step<H, W, true, false>(b, live && going, going, lm.up, lm.dn, cst, pcst, rng_lds, rowl ? g : 0, p, jump);
@@ -1902,7 +1748,6 @@ __global__ __launch_bounds__(64) void k_occupancy_rowlane(const u16 *__restrict_
             }
         }
         if (!__ballot(going && s >= my_pre)) continue;          // nobody counts yet
-#ifndef SL_OCC_NOCOUNT
         if constexpr (PLANES) {
             // Counting.  Every step: the cells that count -- alive, not agent / frozen / exit (advance_board.c:176-181)
             // -- bump small bit-sliced counters that live in registers, one 4-bit counter per cell and colour slot
@@ -1956,7 +1801,6 @@ __global__ __launch_bounds__(64) void k_occupancy_rowlane(const u16 *__restrict_
                                            __HIP_MEMORY_SCOPE_WAVEFRONT);
             }
         }
-#endif
         if (++since_drain == Oc::FLUSH_EVERY) {         // (wave-uniform) 8-bit counters are about to wrap
             since_drain = 0;
             wave_sync();
@@ -1966,7 +1810,7 @@ __global__ __launch_bounds__(64) void k_occupancy_rowlane(const u16 *__restrict_
     }
     if constexpr (PLANES) flush_mini();
     wave_sync();
-    if (live && !Oc::DIRECT) {
+    if (live) {
         if (Oc::CB == 8) {
             occ_drain<H, W, SLOTS>(cnt, dst, inv);
         } else {            // nothing was drained on the way: plain stores, the output need not be zeroed
@@ -2506,7 +2350,8 @@ struct BoardBox {
     int qslot;          // leader -> rows: slot of the finished-episode queue that takes the board, or -1
     int score0;         // rows -> leader: score of the freshly loaded level
     int any;            // (box 0 only) bit 0: some board of the workgroup resets, bit 1: some board is queued
-    int dirty;          // rows -> everyone: the CA changed a cell of the board in this launch (or a level was loaded)
+    int dirty;          // rows -> nobody: the board changed in this launch.  (Written, never read, since the sparse store
+                        // went: the two stores stay for as long as the kernels' instructions are to stay as they are.)
 };
 static_assert(sizeof(BoardBox) == 32, "mailbox stride");
 
@@ -2529,12 +2374,6 @@ static_assert(sizeof(BoardBox) == 32, "mailbox stride");
 // for the compiler to hoist: left as a loop, every loop-invariant address and constant of the RARE blocks (reset, exit
 // tables, queue, the division by the pool size) is computed ahead of the loop by every wave of every launch --
 // some 150 instructions between the load barrier and the first CA pass.
-//
-// LEADX (the LEAN variants of the narrow shapes): the leader wave is a FIFTH wavefront that holds no rows, so the
-// move is in the image as soon as the spans have landed, and what the leaders do around the scores overlaps the rows'
-// CA instead of following it.
-template <int H, int W, bool LEAN>
-constexpr bool leadx() { return LEAN && Geom<H, W>::LEADX_OK; }
 
 // ---- the goal-word cache (round 5) ----------------------------------------------------------------------------------
 // Goals are static in nearly every level (safelife_game.py:753-760 finds that out once per episode), yet every launch
@@ -2572,18 +2411,13 @@ struct GoalCache {
     }
 };
 
-#ifndef SL_SPAWN_GSH_REG
-#define SL_SPAWN_GSH_REG 1      /* A/B knob: the LEAN single-step spawner variant keeps the goal words in registers (1) or
-                                   takes the move box (0) -- both together tip it into scratch */
-#endif
 // the goal colours of a lane's row live in registers (else in the OFF_GSH region of LDS)
 template <int H, int W>
 constexpr bool gsh_in_registers(bool spawn, bool lean, bool one) {
-    return !spawn || Geom<H, W>::WAVES_PER_SIMD < 4 || (SL_SPAWN_GSH_REG && one && lean && W <= 25);
+    // (the LEAN single-step spawner variant keeps the goal words in registers rather than take the move box: both
+    //  together tip it into scratch)
+    return !spawn || Geom<H, W>::WAVES_PER_SIMD < 4 || (one && lean && W <= 25);
 }
-#ifndef SL_LEAN_LDS
-#define SL_LEAN_LDS 1           /* A/B knob: 0 = every variant asks for the full LDS layout (rounds 1-3) */
-#endif
 // LEAN variants whose goal words live in registers use nothing of the OFF_GSH region (no observation parks its
 // parameters there, no wrapper its baseline rows): the score table and the move box move down into it and the
 // workgroup asks for 13 KB less (25x25: 37.7 -> 24.4 KB).  The four workgroups a CU holds of the four-queue step then
@@ -2593,31 +2427,28 @@ constexpr bool gsh_in_registers(bool spawn, bool lean, bool one) {
 // queue shares that pipe stands still (profiles/round4_g_*).
 template <int H, int W>
 constexpr bool lean_lds(bool spawn, bool lean, bool one) {
-    return SL_LEAN_LDS && lean && gsh_in_registers<H, W>(spawn, lean, one);
+    return lean && gsh_in_registers<H, W>(spawn, lean, one);
 }
 template <int H, int W>
 constexpr int lean_lds_bytes() { return Geom<H, W>::OFF_GSH + 4096 + Geom<H, W>::NB * 16; }
 // the plain single-step kernels whose goal words live in registers: goal-word cache, no goal image in LDS
 template <int H, int W>
 constexpr bool nogoals_lds(bool spawn, bool lean, bool one) {
-    return lean && one && !Geom<H, W>::LEADX_OK && gsh_in_registers<H, W>(spawn, lean, one);
+    return lean && one && gsh_in_registers<H, W>(spawn, lean, one);
 }
 template <int H, int W>
 constexpr int nogoals_shift() { return Geom<H, W>::REGION - 16; }
 
-#ifndef SL_WIDE_WAVES
-#define SL_WIDE_WAVES 4         /* A/B knob: waves per SIMD the plain single-step kernels of the wide shapes are compiled for (2: rounds 1-4;
-                                   3: round 5; 4 since the goal words stay packed in registers -- 64x64 without spawners 141 -> 123 registers,
-                                   so that all four workgroups a CU gets of a four-queue step are resident at once; the spawner variants
-                                   of 48- and 64-cell rows do not fit 128 and stay at 3) */
-#endif
+// waves per SIMD the plain single-step kernels of the wide shapes are compiled for (2: rounds 1-4; 3: round 5; 4 since the
+// goal words stay packed in registers -- 64x64 without spawners 141 -> 123 registers, so that all four workgroups a CU
+// gets of a four-queue step are resident at once; the spawner variants of 48- and 64-cell rows do not fit 128 and stay
+// at 3)
 template <int H, int W>
-constexpr int wide_waves(bool spawn) { return spawn && Geom<H, W>::WS > 20 ? (SL_WIDE_WAVES < 3 ? SL_WIDE_WAVES : 3) : SL_WIDE_WAVES; }
+constexpr int wide_waves(bool spawn) { return spawn && Geom<H, W>::WS > 20 ? 3 : 4; }
 template <int H, int W, bool LDS_LUT, bool SPAWN, bool WRAP, bool LEAN, bool ONE>
-__global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
-                             (leadx<H, W, LEAN>() ? 5
-                              : (Geom<H, W>::WAVES_PER_SIMD < 4 && nogoals_lds<H, W>(SPAWN, LEAN, ONE)) ? wide_waves<H, W>(SPAWN)
-                                                                                                       : Geom<H, W>::WAVES_PER_SIMD)) void k_env_rollout_rowlane(
+__global__ __launch_bounds__(64 * WAVES,
+                             ((Geom<H, W>::WAVES_PER_SIMD < 4 && nogoals_lds<H, W>(SPAWN, LEAN, ONE)) ? wide_waves<H, W>(SPAWN)
+                                                                                                      : Geom<H, W>::WAVES_PER_SIMD)) void k_env_rollout_rowlane(
     // the eight arguments the prologue needs before anything else come first: with
     // -amdgpu-kernarg-preload-count=8 they arrive in SGPRs with the wave instead of behind an s_load
     const u16 *__restrict__ hot_board, const u16 *__restrict__ hot_goals, const sl_pcg64 *__restrict__ hot_rng,
@@ -2645,16 +2476,11 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
     constexpr int WS = Gm::WS, HW = Gm::HW;
     const int T = ONE ? 1 : T_arg;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-#ifndef SL_SCALAR_WAVE
-#define SL_SCALAR_WAVE 1        /* A/B knob: the wave's index as a scalar (uniform branches and scalar DMA addresses in the prologue) */
-#endif
-#ifndef SL_PRIO_PROLOGUE
-#define SL_PRIO_PROLOGUE 0      /* A/B knob: s_setprio of every wave until its loads have been issued */
-#endif
-    if (SL_PRIO_PROLOGUE) __builtin_amdgcn_s_setprio(SL_PRIO_PROLOGUE);
     const int tid = threadIdx.x, lane = tid & 63;
+    // the wave's index as a scalar: uniform branches and scalar DMA addresses in the prologue
     // (the plain single-step kernels only: the others sit at their register limit, and a scalar there tips them into scratch)
-    const int wave = (SL_SCALAR_WAVE && ONE && LEAN) ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
+    // (round 5, measured and dropped: s_setprio of every wave until its loads have been issued, and of the leader wave)
+    const int wave = (ONE && LEAN) ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     // envs [hot_first, hot_end) of the batch: one slice (slhip_env_step_slices) or all of it
     const unsigned B = tstride;                        // row pitch of the [T, B] per-step arrays
     const int E = hot_E;
@@ -2666,7 +2492,6 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
     const bool rowl = lane < Gm::NL && gb < nbb;       // holds a row: its own, or a halo copy (V_SHIFT)
     const bool live = rowl && lm.real;                 // owns row r of board gb
     const bool rlead = live && r == 0;                 // the row lane that writes the board's mailbox
-    constexpr bool LEADX = leadx<H, W, LEAN>();
     // The plain single-step kernels keep the lanes' goal words across launches (GoalCache) and NO goal image in LDS
     // (NOGOALS): a launch on cached words needs none, and the rare launch that does need goal rows -- no cache yet, an
     // evolving goal array, a level being loaded -- moves them between registers and global memory row by row.
@@ -2675,21 +2500,7 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
     constexpr bool NOGOALS = nogoals_lds<H, W>(SPAWN, LEAN, ONE);
     static_assert(!NOGOALS || (LEAN && !WRAP), "the goal-image-free layout is the plain kernels'");
     unsigned char *const smem_hi = smem - (NOGOALS ? Gm::REGION - 16 : 0);
-    const bool lwave = wave == (LEADX ? WAVES : 0);    // the leader wave ...
-#ifndef SL_LEADER_PRIO
-#define SL_LEADER_PRIO 0        /* A/B knob: s_setprio of the leader wave (it holds rows AND leads: the wave its workgroup waits for) */
-#endif
-    if (SL_LEADER_PRIO && __builtin_amdgcn_readfirstlane(tid >> 6) == (LEADX ? WAVES : 0)) __builtin_amdgcn_s_setprio(SL_LEADER_PRIO);
-    const bool rwave = !(LEADX && lwave);              // waves that hold rows
-    // SL_SPARSE_STORE (measured, off): single-step launches store only the boards the CA changed -- in a level of
-    // still lifes 57 % of the boards of a step are untouched apart from the agent's own cells, which the leaders then
-    // store themselves -- i.e. half the write traffic and half the dirty lines at the kernel boundary.  Bit-exact
-    // (suite + soak), and no faster: 8.01-8.09 vs 7.91 us per two-slice C3 step in one session (the per-chunk test
-    // and 14 more registers cost what the bytes save).
-#ifndef SL_SPARSE_STORE
-#define SL_SPARSE_STORE 0
-#endif
-    constexpr bool SPARSE_STORE = SL_SPARSE_STORE && ONE && use_planes<H, W>() && !Gm::SWZ;
+    const bool lwave = wave == 0;                      // the leader wave ...
     const bool lead = lwave && lane < nbb;             // ... whose lane q is the leader of board q
     const int lq = lead ? lane : 0;
     const unsigned e = e0b + (rowl ? gb : 0);          // the row lane's env
@@ -2710,7 +2521,7 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
     constexpr int OFF_LUT_V = SHRINK ? Gm::OFF_GSH : Gm::OFF_LUT, OFF_MOVE_V = SHRINK ? Gm::OFF_GSH + 4096 : Gm::OFF_MOVE;
     // (round 6) the kernels that keep the goal-word cache hold the words as the cache does, five to a dword (goal_unpack):
     // what lives from the prologue's loads to the score is 3 registers at 25x25 and 7 at 64x64 instead of 13 and 32
-    constexpr bool GPK = LEAN && GSH_REG && ONE && !LEADX;
+    constexpr bool GPK = LEAN && GSH_REG && ONE;
     u32 gsh_reg[GSH_REG ? (GPK ? (WS + 4) / 5 : WS) : 1];
     u32 *gsh_lane = GSH_REG ? gsh_reg : (u32 *)(smem_hi + Gm::OFF_GSH) + (wave * 64 + lane) * WS;
     auto set_goal_words = [&](const RowWords<H, W> &g) {        // g: the goal cells of the lane's row
@@ -2724,7 +2535,7 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
     // the goal-word cache (GoalCache above): LEAN kernels whose goal words live in registers
     // (single-step launches: the T-step instantiations sit at their register limit -- a T-step launch of a batch that
     //  has a cache lowers every flag first, launch_rollout_t)
-    constexpr bool GCACHE = LEAN && GSH_REG && ONE && !LEADX;
+    constexpr bool GCACHE = LEAN && GSH_REG && ONE;
     static_assert(GCACHE == NOGOALS, "the kernels that keep the cache are the ones without a goal image");
     static_assert(GCACHE == GPK, "the kernels that keep the cache hold the words in its packed form");
     using Gc = GoalCache<H, W>;
@@ -2736,11 +2547,9 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
     // The flag is FETCHED here, first thing, and LOOKED AT where the goal span would be issued (gc_look below) -- behind
     // the record loads and the board's DMA instructions, so that its round trip runs under them.
     u32 gc_word = 0;
-#ifndef SL_GOALS_FIRST
-#define SL_GOALS_FIRST 1        /* A/B knob: 0 = the goal words are asked for behind the flag's round trip (round 5) */
-#endif
-    // (both knobs: the narrow shapes only -- at 64x64 either costs C5's step 1 %, 24.2 against 23.9 us)
-    constexpr bool GOALS_FIRST = SL_GOALS_FIRST && Gm::WAVES_PER_SIMD == 4;
+    // (GOALS_FIRST and ARGS_EARLY: the narrow shapes only -- at 64x64 either costs C5's step 1 %, 24.2 against 23.9 us;
+    //  round 5 asked for the goal words behind the flag's round trip everywhere, as the wide shapes still do)
+    constexpr bool GOALS_FIRST = Gm::WAVES_PER_SIMD == 4;
     if (GCACHE && gc_flag && T > 0) {
         gc_word = *(const u32 *)gc_flag;
         // (round 6) ... and the lane's goal words with it, BEFORE the flag says whether they are any good (a block has
@@ -2809,13 +2618,10 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
     int pre_i[4] = {0, 0, 0, 0}, pre_y1 = 0, pre_x1 = 0;   // the move of step 0, on cells taken from global memory
     u32 pre_c[4] = {0u, 0u, 0u, 0u};
     bool pre_write = false;
-#ifndef SL_ARGS_EARLY
-#define SL_ARGS_EARLY 1         /* A/B knob: 0 = the leader wave fetches the kernel arguments where the loading waves do (round 5) */
-#endif
     // Every kernel argument the rest of the kernel needs that did not arrive preloaded: fetched in ONE batch, in the
     // shadow of the bulk loads -- by the loading waves behind their DMA instructions, by the leader wave (round 6) behind
     // the loads of its first round trip: behind the look at the flag it stood, 0.15 us, on the leaders' way to the barrier.
-    constexpr bool ARGS_EARLY = SL_ARGS_EARLY && Gm::WAVES_PER_SIMD == 4;
+    constexpr bool ARGS_EARLY = Gm::WAVES_PER_SIMD == 4;
     auto fetch_args = [&]() {
         const int a0 = env.time_limit, a1 = env.exit_points, a2 = env.auto_reset, a3 = env.L, a4 = env.level_stride;
         const int a5 = env.B, a6 = env.stream_salt, a7 = env.out_compact;
@@ -2824,19 +2630,13 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
         asm volatile("" ::"s"(a0), "s"(a1), "s"(a2), "s"(a3), "s"(a4), "s"(T), "s"(p0), "s"(p1), "s"(p2), "s"(p3),
                      "s"(p4), "s"(p5), "s"(p6), "s"(reward_t), "s"(done_t), "s"(xcd_base), "s"(xcd_flag), "s"(a5), "s"(a6), "s"(a7));
     };
-#ifndef SL_MOVE_BOX
-#define SL_MOVE_BOX 1           /* A/B knob: 0 = the round-3 form of the move (leader writes the image, a barrier of its own) */
-#endif
-#ifndef SL_MOVE_LDS
-#define SL_MOVE_LDS 1           /* A/B knob: 0 = the move's cells come from global memory, in front of the load barrier (round 4) */
-#endif
     // (round 6) single-step launches: the leaders take the four cells of their move from the IMAGE, right behind the load
     // barrier, and the rows wait at a second barrier for the move to be in it.  Fetched from global memory ahead of the
     // barrier (round 4) the cells are a second round trip behind the record's -- 0.80 -> 1.4 us after the wave's start,
     // while the loading waves have the whole board in LDS at 1.05 (profiles/round6_t4_leader_path_trace.txt).
     // (not the wrappers' kernels: the "inaction" baseline copies the board as it stands BEFORE the move, inside the step
     //  loop; not the wide shapes: at 64x64 the second barrier costs more than the round trip, 23.7 against 23.45 us per C5 step)
-    constexpr bool MOVE_LDS = SL_MOVE_LDS && SL_MOVE_BOX && ONE && !WRAP && Gm::WAVES_PER_SIMD == 4;
+    constexpr bool MOVE_LDS = ONE && !WRAP && Gm::WAVES_PER_SIMD == 4;
     if (lwave) {
         ly = hot_scalars[el].agent_row;
         lx = hot_scalars[el].agent_col;
@@ -2864,8 +2664,8 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
         SL_STAMP(13);       // (trace builds, leader wave: the goal-word flag is in)
     } else {
         // everything bulky goes through the LDS DMA, issued by the waves that are not the leader
-        constexpr int DW = LEADX ? WAVES : WAVES - 1;
-        const int dw = LEADX ? wave : wave - 1;
+        constexpr int DW = WAVES - 1;
+        const int dw = wave - 1;
         dma_to_lds<Gm::NB * 32, false, DW>((const unsigned char *)(k_rng + e0b), smem_hi + Gm::OFF_RNG, nbb * 32, lane, dw);
         dma_to_lds<Gm::NB * 64, false, DW>((const unsigned char *)(hot_scalars + e0b), smem_hi + Gm::OFF_REC, nbb * 64, lane, dw);
         // (the score table's pointer is not preloaded: where the flag is looked at anyway, its DMA goes behind that wait)
@@ -2901,7 +2701,7 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
 #pragma unroll
         for (int j = 0; j < Gc::TAIL; ++j) gsh_reg[4 * Gc::X4 + j] = *Gc::tail(gc_block, wave, lane, j);
     }
-    constexpr bool MOVE_BOX = !MOVE_LDS && SL_MOVE_BOX && ONE && !(SPAWN && GSH_REG && Gm::WAVES_PER_SIMD == 4);
+    constexpr bool MOVE_BOX = !MOVE_LDS && ONE && !(SPAWN && GSH_REG && Gm::WAVES_PER_SIMD == 4);
     // (Round 4, measured and dropped -- as round 3's variant of it was: every wave sending its OWN boards to global
     //  memory right behind its CA pass, under the score phase and the leaders' work, the leaders storing the agent's
     //  and the exits' cells themselves behind the end barrier.  Same-box A/B, K = 400: 6.47-6.52 us per step without,
@@ -2938,7 +2738,6 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
         if (lead) move_box[lq] = mv;
     }
     SL_STAMP(1);
-    if (SL_PRIO_PROLOGUE) __builtin_amdgcn_s_setprio(0);
     // the load barrier: the DMA waves wait for their loads, the leader wave only for its LDS stores (it moved none
     // of the spans, and what it has in flight is its own business)
     if (lwave) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -2985,7 +2784,6 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
 #pragma unroll
     for (int k = 0; k < WS; ++k) asm volatile("" : "=v"(b[k]));
     if (GCACHE && goals_free) gstatic = 1;           // (what the flag vouches for; the goal image does not exist in this launch)
-    if (rwave) {
     if (live && !goals_free) {
         if constexpr (NOGOALS) read_row_global<H, W>(k_goals + (size_t)e * HW + r * W, b);
         else read_row<H, W>(goals, gb, r, b);
@@ -3006,7 +2804,6 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
         if (rowl && gstatic == 0 && restless == 0) gstatic = 1;
     }
     if (rlead) box[gb].gstat = gstatic;
-    }
     SL_STAMP(3);
 
     // What the leaders ask of the rows at the end of a step -- queue the finished episode's board, load the next
@@ -3175,7 +2972,7 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
             // An env in the first step of an episode (num_steps == 0) takes its board as it stands now -- after the
             // reset, before this step's action -- as its baseline: what the wrapper's reset() copies.
             const bool fresh = rowl && ((const sl_env_scalars *)(smem_hi + Gm::OFF_REC))[gb].num_steps == 0;
-            if (rwave && __ballot(fresh)) {
+            if (__ballot(fresh)) {
                 if (fresh && live) {
                     read_row<H, W>(board, gb, r, b);
                     write_row<H, W>(inb, gb, r, b);
@@ -3183,7 +2980,7 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
             }
             if (!MOVE_BOX && !MOVE_LDS) wg_sync();           // (the leaders write the move into the image: behind the rows' reads)
         }
-        if (MOVE_BOX && rwave && rlead) {
+        if (MOVE_BOX && rlead) {
             // the move the board's leader decided: into the image, by the board's own wave, ahead of its row reads
             // (one 16-byte read: four dependent read -> write round trips in a loop cost 0.3 us on the step's chain)
             const u32x4_t mv = move_box[gb];
@@ -3214,13 +3011,11 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
         }                                          // (single-step launches: it went in behind the load barrier)
         SL_STAMP(4);
         // safelife_env.py:152 : board first, then goals unless they are static (safelife_game.py:746-761)
-        if (rwave) {
         const bool dyn = rowl && gstatic != 1;
         const int goal_pass = __ballot(dyn) ? 1 : -1;
         // (WRAP, "inaction": one more pass, over the baseline boards with the baselines' own generators)
         const int base_pass = (WRAP && inaction) ? (goal_pass > 0 ? 2 : 1) : -1;
         const int passes = 1 + (goal_pass > 0 ? 1 : 0) + (base_pass > 0 ? 1 : 0);
-        bool board_dirty = !SPARSE_STORE;
 #pragma nounroll
         for (int pass = 0; pass < passes; ++pass) {
             const bool base = WRAP && pass == base_pass;
@@ -3244,14 +3039,6 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
                 else
                 changed = ca_step<H, W, SPAWN, false>(b, mine, mine, up, dn, cst, pcst, pass_rng, live ? g : 0, p, jump,
                                                       &row_changed);
-                if (SPARSE_STORE && pass == 0) {             // which of the wave's boards changed
-                    const unsigned long long rows = __ballot(mine && row_changed != 0);
-#pragma unroll
-                    for (int q = 0; q < Gm::G; ++q) {
-                        const unsigned long long of_q = ((Gm::GL == 64 ? ~0ull : ((1ull << Gm::GL) - 1ull)) << (q * Gm::GL % 64));
-                        if (g == q) board_dirty = (rows & of_q) != 0;
-                    }
-                }
             } else {
                 // (column-first reduction where its three arrays fit beside the row: not at 15-16 words with 128 registers)
                 constexpr bool COLFIRST = LEAN && !SPAWN && (WS <= 13 || Gm::WAVES_PER_SIMD < 4);
@@ -3311,11 +3098,9 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
         if (rlead) {
             box[gb].score = score_rows;
             box[gb].gstat = gstatic;
-            box[gb].dirty = board_dirty ? 1 : 0;
+            box[gb].dirty = 1;
         }
-        }
-        // the leaders: what does not depend on the scores is read before the barrier (in the LEADX kernels, under
-        // the rows' CA pass)
+        // the leaders: what does not depend on the scores is read before the barrier
         int b_initial = 0, b_required = 0, b_old_value = 0, b_steps = 0, b_ep_len = 0;
         float b_ep_rew = 0.0f;
         bool b_active = false;
@@ -3387,27 +3172,6 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
                 if (reward_t) reward_t[(size_t)t * B + el] = reward;
                 if (done_t) done_t[(size_t)t * B + el] = done;
 #endif
-                if (SPARSE_STORE && env.auto_reset && done) {
-                    box[lq].dirty = 1;      // a level is about to be loaded over this board: the span store takes it all
-                } else if (SPARSE_STORE && !box[lq].dirty) {
-                    // the rows changed nothing on this board: what the move and the repaint touched goes to global
-                    // memory cell by cell (the values are in registers: with the CA idle the move's cells are as
-                    // the move left them)
-                    u16 *gdst = env.board + (size_t)el * HW;
-                    if (pre_write) {
-                        gdst[pre_i[0]] = (u16)pre_c[0];
-                        gdst[pre_i[1]] = (u16)pre_c[1];
-                        gdst[pre_i[2]] = (u16)pre_c[2];
-                        gdst[pre_i[3]] = (u16)pre_c[3];
-                    }
-                    if (ly >= 0) gdst[Gm::cell(ly, lx)] = (u16)cell;
-                    const u16 paint = (u16)(FROZEN | EXIT | (w_open ? COLOR_R : 0u));
-                    if (exit0 >= 0) gdst[exit0] = paint;
-                    for (int k = 1; k < E; ++k) {
-                        const int ex = exits[k];
-                        if (ex >= 0) gdst[ex] = paint;
-                    }
-                }
                 if (hand_over) {
                     int slot = -1, next_level = -1, any = 0;
                     if (has_queue && ended) {
@@ -3511,11 +3275,13 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
     int tid2 = tid;
     asm volatile("" : "+v"(tid2));
     const int lane2 = tid2 & 63, wave2 = tid2 >> 6;
-    if (rwave) {
-        if constexpr (SPARSE_STORE) store_span_dirty<H, W>(env.board + (size_t)e0b * HW, board, nbb, tid2, box);
-        else store_span<H, W>(env.board + (size_t)e0b * HW, board, nbb, tid2);
-        if (dirty && !NOGOALS) store_span<H, W>(env.goals + (size_t)e0b * HW, goals, nbb, tid2);
-    }
+    // (round 3, measured and dropped: single-step launches storing only the boards the CA changed -- in a level of still
+    //  lifes 57 % of the boards of a step are untouched apart from the agent's own cells, which the leaders then store
+    //  themselves -- i.e. half the write traffic and half the dirty lines at the kernel boundary.  Bit-exact, and no
+    //  faster: 8.01-8.09 against 7.91 us per two-slice C3 step in one session, re-measured in round 6 7.30-7.34 against
+    //  6.65-6.68: the per-chunk test and 14 more registers cost what the bytes save)
+    store_span<H, W>(env.board + (size_t)e0b * HW, board, nbb, tid2);
+    if (dirty && !NOGOALS) store_span<H, W>(env.goals + (size_t)e0b * HW, goals, nbb, tid2);
     if (GCACHE && gc_flag && T != 0) {
         // GoalCache: a launch that had the goal span keeps the lanes' words if every board of the workgroup ends it with
         // static goals (the words in the registers are current: a reset and an evolving goal both rewrite them); a
@@ -3526,7 +3292,7 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
 #pragma unroll
             for (int q = 0; q < Gm::NB; ++q)
                 if (q < nbb && box[q].gstat != 1) all_static = false;
-            if (all_static && rwave && live && (nbb == Gm::NB || e0b + nbb >= env.B)) {
+            if (all_static && live && (nbb == Gm::NB || e0b + nbb >= env.B)) {
 #pragma unroll
                 for (int c = 0; c < Gc::X4; ++c)
                     *Gc::x4(gc_block, wave2, lane2, c) = u32x4{gsh_reg[4 * c], gsh_reg[4 * c + 1], gsh_reg[4 * c + 2], gsh_reg[4 * c + 3]};
@@ -3548,7 +3314,7 @@ __global__ __launch_bounds__(64 * (WAVES + (leadx<H, W, LEAN>() ? 1 : 0)),
         for (int i = tid2; i < nbb * (int)(sizeof(sl_wrap_state) / 4); i += 64 * WAVES)
             ((u32 *)(env.wrap.state + e0b))[i] = ((const u32 *)wst)[i];
     if (WRAP && inaction && T > 0) {
-        if (rwave) store_span<H, W>(env.wrap.inaction_board + (size_t)e0b * HW, inb, nbb, tid2);
+        store_span<H, W>(env.wrap.inaction_board + (size_t)e0b * HW, inb, nbb, tid2);
         if (lane2 < 4 * Gm::G && wave2 * Gm::G + (lane2 >> 2) < nbb)
             ((u64 *)(env.wrap.inaction_rng + e0b + wave2 * Gm::G))[lane2] =
                 ((const u64 *)(smem_hi + OFF_INB + Gm::REGION) + 4 * Gm::G * wave2)[lane2];
@@ -3745,8 +3511,7 @@ static_assert(sizeof(RolloutArgs) <= sizeof(PreparedStep::args), "argument block
 
 // variant selection, LDS size and the module-level handle of the kernel that steps `env` (T steps per launch)
 template <int H, int W>
-hipError_t pick_rollout_t(const sl_env_batch &env, int T, void **kernel, hipFunction_t *f_out, unsigned *threads_out, int *lds_out,
-                          bool *gcache_ok) {
+hipError_t pick_rollout_t(const sl_env_batch &env, int T, void **kernel, hipFunction_t *f_out, int *lds_out, bool *gcache_ok) {
     using Gm = Geom<H, W>;
     const bool lean = !env.wrap.flags && !env.obs && !env.policy_obs && (env.finished.capacity == 0 || Gm::WAVES_PER_SIMD < 4);
     const int variant = (env.n_tables == 1 ? 1 : 0) | (env.spawner_free ? 2 : 0) | (env.wrap.flags ? 4 : (lean ? 8 : 0));
@@ -3763,11 +3528,10 @@ hipError_t pick_rollout_t(const sl_env_batch &env, int T, void **kernel, hipFunc
     static const kernel_t table[24] = {SL_VARIANTS(false), SL_VARIANTS(true)};
 #undef SL_VARIANTS
     const int slot = variant + (T == 1 ? 12 : 0);
-    *threads_out = 64 * (WAVES + ((variant & 8) && Gm::LEADX_OK ? 1 : 0));     // LEAN: a fifth, leader wave
     const kernel_t fn = table[slot];
     const bool spawn = !(variant & 2), base_in_gsh = !spawn && Gm::WAVES_PER_SIMD == 4;
     // (the kernel's GCACHE: LEAN instantiations whose goal words live in registers)
-    *gcache_ok = (variant & 8) && T == 1 && gsh_in_registers<H, W>(spawn, true, true) && !Gm::LEADX_OK;
+    *gcache_ok = (variant & 8) && T == 1 && gsh_in_registers<H, W>(spawn, true, true);
     const int lds_wrap = base_in_gsh ? Gm::LDS_WRAP_GSHREG : Gm::LDS_WRAP_GSHLDS;
     // (the plain single-step kernels keep no goal image: nogoals_lds)
     const bool nogoals = (variant & 8) && T == 1 && nogoals_lds<H, W>(spawn, true, true);
@@ -3817,10 +3581,10 @@ hipError_t launch_rollout_t(const sl_env_batch &env, int e_first, int e_count, c
     using Gm = Geom<H, W>;
     void *kernel = nullptr;
     hipFunction_t f = nullptr;
-    unsigned threads = 0;
+    const unsigned threads = 64 * WAVES;
     int lds = 0;
     bool gcache_ok = false;
-    hipError_t err = pick_rollout_t<H, W>(env, T, &kernel, &f, &threads, &lds, &gcache_ok);
+    hipError_t err = pick_rollout_t<H, W>(env, T, &kernel, &f, &lds, &gcache_ok);
     if (err != hipSuccess) return err;
     const unsigned grid = (unsigned)((e_count + Gm::NB - 1) / Gm::NB);
     // the goal-word cache (GoalCache): handed to launches whose workgroups coincide with its blocks.  Any other launch of
@@ -3926,11 +3690,11 @@ bool rowlane_lean_takes_queue(int H, int W) {
 size_t rowlane_goal_cache_bytes(int H, int W, int B, bool spawn, int *boards_per_block) {
     // (slices and queue slices start at multiples of 64 envs: shapes whose workgroups hold 12, 20 or 24 boards would have
     //  launches off the blocks' grid -- they go without a cache; and so do batches whose plain single-step kernel keeps
-    //  none -- the kernel's GCACHE: goal words in registers, no fifth leader wave)
+    //  none -- the kernel's GCACHE: goal words in registers)
 #define X(h, w)                                                         \
     if (H == h && W == w) {                                             \
         if (64 % rl::Geom<h, w>::NB != 0) break;                        \
-        if (!rl::gsh_in_registers<h, w>(spawn, true, true) || rl::Geom<h, w>::LEADX_OK) break; \
+        if (!rl::gsh_in_registers<h, w>(spawn, true, true)) break;      \
         if (boards_per_block) *boards_per_block = rl::Geom<h, w>::NB;   \
         return rl::GoalCache<h, w>::bytes(B);                           \
     }
