@@ -936,6 +936,98 @@ int slhip_rollout_gather(const sl_rollout_multi *buf, const long long *rows, lon
                          long long *actions_out, float *action_prob_out, float *returns_out, float *advantages_out,
                          float *values_out, void *stream);
 
+/* ---- level schedules: task switching, curricula, exit difficulty (additive to ABI 13: four new symbols and one new
+ * struct, nothing existing changes, so SL_ABI_VERSION stays where it is) --------------------------------------------------
+ * The reference's trainers draw every reset's level family from a schedule (training/env_factory.py: the coin of
+ * SwitchingLevelIterator :155-174 with a scheduled probability, the softmax over recent slopes of performance of
+ * CurricularLevelIterator :51-146) and scale every level's min_performance by a LinearSchedule of the training step
+ * (MinPerformanceScheduler, :363-373).  Here the pool is a large pre-generated library that stays resident, cut into G
+ * groups -- group g is the slot range [start[g], start[g] + len[g]), ranges disjoint, every len >= 1, slots outside every
+ * group are never drawn -- and the step kernels stay as they are: these entry points rewrite what they read at launch
+ * time, sl_env_batch.pool_next and pool_scalars[l].required_step, between two steps.
+ *
+ * The draw is PER SLOT AND STEP, not per env: two envs whose episodes end on the same slot in the same step load the same
+ * successor (their random streams still differ through sl_env_batch.stream_salt).  The reference's envs share one iterator
+ * queue, so neither side promises independent draws per env.
+ *
+ * The struct lives on the host; every pointer is a device pointer. */
+#define SL_SCHEDULE_MAX_GROUPS 8
+#define SL_SCHEDULE_MAX_LOOKBACK 1024
+#define SL_SCHEDULE_BAD_PROBS 1   /* bit of *status: slhip_schedule_draw met device probabilities with a negative or
+                                     non-finite entry, or a sum that is 0 or not finite, and drew uniformly over the groups */
+typedef struct sl_level_schedule { /* 168 bytes */
+    int32_t G;                    /* groups, 1 .. SL_SCHEDULE_MAX_GROUPS */
+    int32_t lookback;             /* records per group ring, 2 .. SL_SCHEDULE_MAX_LOOKBACK (the reference: 100) */
+    int32_t L;                    /* slots of the pool (sl_env_batch.L): every group lies inside [0, L) */
+    int32_t reserved;
+    int32_t start[SL_SCHEDULE_MAX_GROUPS];
+    int32_t len[SL_SCHEDULE_MAX_GROUPS];
+    /* per pool slot, from the host */
+    const double *min_performance;   /* [L] the level's own min_performance (slhip_schedule_required) */
+    const int32_t *available;        /* [L] GameWithGoals.initial_available_points of agent 0 (slhip_schedule_required) */
+    const int32_t *reward_possible;  /* [L] available + points_on_level_exit (safelife_logger.py:286-294; harvest) */
+    /* per env */
+    int32_t *cur_slot;            /* [B] the slot the env's running episode was loaded from */
+    /* per group (CurricularLevelIterator.perf_records / .best): a fresh schedule has ring[g][0] = 0.0, count = 1, pos = 1
+       -- the reference's default record [0.0] -- and everything else 0 */
+    double *ring;                 /* [G, lookback] */
+    long long *count;             /* [G] records appended so far, the first 0.0 included */
+    long long *episodes;          /* [G] episodes harvested */
+    int32_t *pos;                 /* [G] where the next record goes = count % lookback */
+    double *best;                 /* [G] the largest performance so far (>= 0: best_perf_lvl*) */
+    double *mean;                 /* [G] mean of the ring's min(count, lookback) records, summed oldest first and divided
+                                     once (recent100_perf_lvl*); written whenever the group takes a record */
+    int32_t *status;              /* [1] SL_SCHEDULE_* bits, only ever raised by the library */
+} sl_level_schedule;
+
+/* pool_next[s] for every slot s in [0, L), one thread per slot.  With z(i) = splitmix64's finalizer of
+ * seed + G64 * (counter * 0x100000001B3 + i + 1) mod 2^64 (G64 = 0x9E3779B97F4A7C15: slhip_sample_actions' construction)
+ *   z1 = z(2 s), z2 = z(2 s + 1);
+ *   u = (z1 >> 11) * 2^-53, a 53-bit uniform in [0, 1);  cum[g] = the float64 running sum p_0 + ... + p_g, in index order;
+ *   t = u * cum[G-1] (one rounding);  g = the first group with cum[g] > t; if rounding leaves none, the last group with
+ *   p_g > 0;  pool_next[s] = start[g] + (the high 64 bits of z2 * len[g]).
+ * A group with p_g == 0 is never drawn.  The member draw's bias is at most len / 2^64.  Slots outside every group are
+ * sources like any other (an env that stands on one moves into a group at its next reload).
+ * probs: HOST pointer to G doubles, passed by value into the launch; a negative, NaN or infinite entry or a sum that is 0
+ * (or overflows) is SL_E_SHAPE.  probs NULL: the device array device_probs [G] (what slhip_schedule_curriculum writes) is
+ * read by the kernel; if it holds a negative or non-finite entry, or sums to 0 or to infinity, the kernel draws with equal
+ * probabilities instead and raises SL_SCHEDULE_BAD_PROBS in *status -- nothing is sampled from garbage.
+ * Needs of *sched: G, L, start, len, status.  L must be sched->L. */
+int slhip_schedule_draw(const sl_level_schedule *sched, const double *probs, const double *device_probs,
+                        unsigned long long seed, unsigned long long counter, int32_t *pool_next, int L, void *stream);
+
+/* pool_scalars[l].required_step = max(0, (int32) ceil((min_performance[l] * fraction) * (double) available[l])) for every
+ * slot l in [0, L): two float64 products, each rounded on its own -- levels.required_points(np.float64(mp) * fraction,
+ * available), i.e. env_wrappers.py:142-145 followed by safelife_game.py:711-714, bit for bit (a NaN gives 0; a value past
+ * int32 gives INT32_MAX).  Nothing else of the record is touched: required_reset and ready depend on the level's own
+ * min_performance.  An env picks the new value up at its next reload, as the reference's wrapper evaluates its schedule
+ * at reset().  fraction must be finite.  Needs of *sched: min_performance, available. */
+int slhip_schedule_required(const sl_level_schedule *sched, double fraction, sl_level_scalars *pool_scalars, int L,
+                            void *stream);
+
+/* After every step.  For every env e with out[e].done, in ascending e: perf = f64(out[e].episode_reward) /
+ * f64(reward_possible[cur_slot[e]]), 0.0 when that is not finite (env_factory.py:95-98), is appended to the ring of the
+ * group cur_slot[e] lies in (ring[g][pos] = perf, pos = (pos + 1) % lookback, count += 1, episodes += 1, best = max(best,
+ * perf)); an env whose cur_slot lies in no group leaves no record.  A record's place is a function of the done flags alone:
+ * no atomic's arrival order takes part.  Then mean[g] is written for every group that took a record, and cur_slot[e] =
+ * scalars[e].level_idx for EVERY env -- after an in-kernel reload that is the new level, which is why the schedule remembers
+ * the old one.  Whoever reloads envs from outside the step (slhip_env_reset) sets their cur_slot from level_idx itself.
+ * `out` takes 16-byte records (not sl_env_batch.out_compact).  One launch. */
+int slhip_schedule_harvest(const sl_level_schedule *sched, const sl_step_out *out, const sl_env_scalars *scalars, int B,
+                           void *stream);
+
+/* CurricularLevelIterator.get_next_parameters (env_factory.py:111-127) in float64 -> probs_out [G] (device):
+ *   tp[g] = 0.2 / lookback while count[g] < lookback; else 10 * m, m the least-squares slope of the ring's records
+ *   y_0 (oldest) .. y_{n-1}, n = lookback, against 0 .. n-1 in closed form: xbar = (n - 1) / 2, sxx = n (n^2 - 1) / 12,
+ *   sxy = sum_i (i - xbar) * y_i in index order, m = sxy / sxx;
+ *   scale = min_g |tp[g]|;  tp = max(tp, 0) / scale, NaN and inf -> 0;  p[g] = exp(tp[g] - max tp) / sum_g exp(...), summed
+ *   in index order.
+ * Everything but exp() is exactly specified.  Where all records of a ring are equal the closed form gives m = 0 exactly
+ * and the reference's polyfit gives rounding noise (which the division by `scale` then blows up): that input is
+ * degenerate in the reference; here every group with tp <= 0 gets tp = 0, and if that makes scale 0 every entry becomes
+ * NaN or inf -> 0 and the probabilities are equal. */
+int slhip_schedule_curriculum(const sl_level_schedule *sched, double *probs_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

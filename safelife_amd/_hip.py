@@ -36,7 +36,10 @@ EXPORTS = (
     "slhip_replay_add_masked", "slhip_sample_actions_eps_masked",
     "slhip_sample_actions_masked", "slhip_rollout_record_multi", "slhip_training_batch_multi",
     "slhip_rollout_compact_chunks", "slhip_rollout_compact", "slhip_rollout_gather",
+    "slhip_schedule_draw", "slhip_schedule_required", "slhip_schedule_harvest", "slhip_schedule_curriculum",
 )
+SCHEDULE_MAX_GROUPS, SCHEDULE_MAX_LOOKBACK = 8, 1024
+SCHEDULE_BAD_PROBS = 1
 REWARD_F32, REWARD_F64 = 0, 1
 ROLLOUT_BAD_ACTION, ROLLOUT_BAD_INDEX = 1, 2
 ROLLOUT_SCAN_CHUNK = 4096
@@ -172,6 +175,14 @@ class Replay(C.Structure):
                                              "win_reward", "fill", "head", "idx", "status", "plan_base", "plan_code")])
 
 
+class LevelSchedule(C.Structure):
+    """struct sl_level_schedule (168 bytes)"""
+    _fields_ = ([(n, C.c_int32) for n in ("G", "lookback", "L", "reserved")]
+                + [("start", C.c_int32 * SCHEDULE_MAX_GROUPS), ("len", C.c_int32 * SCHEDULE_MAX_GROUPS)]
+                + [(n, C.c_void_p) for n in ("min_performance", "available", "reward_possible", "cur_slot", "ring", "count",
+                                             "episodes", "pos", "best", "mean", "status")])
+
+
 class EnvBatch(C.Structure):
     _fields_ = (
         [(n, C.c_int32) for n in ENV_SCALARS_HEAD]
@@ -280,6 +291,11 @@ def lib():
         L.slhip_rollout_compact.argtypes = [C.POINTER(RolloutMulti), _p, _p, _p, _p]
         L.slhip_rollout_gather.argtypes = [C.POINTER(RolloutMulti), _p, C.c_longlong, _p, _p, _p, C.c_longlong, _p,
                                            _p, _p, _p, _p, _p, _p]
+        L.slhip_schedule_draw.argtypes = [C.POINTER(LevelSchedule), C.POINTER(C.c_double), _p, C.c_ulonglong, C.c_ulonglong,
+                                          _p, C.c_int, _p]
+        L.slhip_schedule_required.argtypes = [C.POINTER(LevelSchedule), C.c_double, _p, C.c_int, _p]
+        L.slhip_schedule_harvest.argtypes = [C.POINTER(LevelSchedule), _p, _p, C.c_int, _p]
+        L.slhip_schedule_curriculum.argtypes = [C.POINTER(LevelSchedule), _p, _p]
         L.slhip_obs_to_policy.argtypes = [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]
         L.slhip_gather_unique_id.argtypes = [_p]
         L.slhip_gather_init.argtypes = [_p, C.c_int, C.c_int, C.POINTER(_p)]

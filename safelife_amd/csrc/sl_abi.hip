@@ -1841,4 +1841,81 @@ int slhip_obs_to_policy(const uint32_t *view, int B, int vh, int vw, const int32
     return err == hipSuccess ? SL_OK : hip_fail(err, "obs_to_policy launch");
 }
 
+// groups: 1..8 disjoint ranges of at least one slot inside [0, L)
+static int check_schedule(const sl_level_schedule *s) {
+    if (!s) return fail(SL_E_ARG, "schedule: null schedule description");
+    const int L = s->L;
+    if (L < 1) return fail(SL_E_SHAPE, "schedule: L must be at least 1");
+    if (s->G < 1 || s->G > SL_SCHEDULE_MAX_GROUPS) return fail(SL_E_SHAPE, "schedule: G outside 1..SL_SCHEDULE_MAX_GROUPS");
+    if (s->lookback < 2 || s->lookback > SL_SCHEDULE_MAX_LOOKBACK)
+        return fail(SL_E_SHAPE, "schedule: lookback outside 2..SL_SCHEDULE_MAX_LOOKBACK");
+    for (int g = 0; g < s->G; ++g) {
+        if (s->len[g] < 1 || s->start[g] < 0) return fail(SL_E_SHAPE, "schedule: a group needs start >= 0 and len >= 1");
+        if ((long long)s->start[g] + s->len[g] > L) return fail(SL_E_SHAPE, "schedule: a group reaches past the pool's last slot");
+        for (int h = 0; h < g; ++h)
+            if (s->start[g] < s->start[h] + s->len[h] && s->start[h] < s->start[g] + s->len[g])
+                return fail(SL_E_SHAPE, "schedule: groups overlap");
+    }
+    return SL_OK;
+}
+
+int slhip_schedule_draw(const sl_level_schedule *sched, const double *probs, const double *device_probs,
+                        unsigned long long seed, unsigned long long counter, int32_t *pool_next, int L, void *stream) {
+    if (int rc = check_schedule(sched)) return rc;
+    if (L != sched->L) return fail(SL_E_SHAPE, "schedule_draw: L is not the schedule's L");
+    if (!pool_next || !sched->status) return fail(SL_E_ARG, "schedule_draw: null pool_next / status");
+    sl::schedule_probs hp = {};
+    if (probs) {
+        double sum = 0.0;
+        for (int g = 0; g < sched->G; ++g) {
+            if (!(probs[g] >= 0.0) || probs[g] > 1.7976931348623157e308)
+                return fail(SL_E_SHAPE, "schedule_draw: a probability is negative, NaN or infinite");
+            hp.p[g] = probs[g];
+            sum += probs[g];
+        }
+        if (!(sum > 0.0) || sum > 1.7976931348623157e308) return fail(SL_E_SHAPE, "schedule_draw: the probabilities sum to 0 (or overflow)");
+    } else if (!device_probs) {
+        return fail(SL_E_ARG, "schedule_draw: neither probs nor device_probs");
+    }
+    const hipError_t err = sl::launch_schedule_draw(*sched, probs ? &hp : nullptr, device_probs, seed, counter, pool_next, L,
+                                                    (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "schedule_draw launch");
+}
+
+int slhip_schedule_required(const sl_level_schedule *sched, double fraction, sl_level_scalars *pool_scalars, int L,
+                            void *stream) {
+    if (!sched) return fail(SL_E_ARG, "schedule_required: null schedule description");
+    if (L < 1 || L != sched->L) return fail(SL_E_SHAPE, "schedule_required: L must be the schedule's L (at least 1)");
+    if (!(fraction - fraction == 0.0)) return fail(SL_E_SHAPE, "schedule_required: fraction is not finite");
+    if (!sched->min_performance || !sched->available || !pool_scalars)
+        return fail(SL_E_ARG, "schedule_required: null min_performance / available / pool_scalars");
+    const hipError_t err = sl::launch_schedule_required(*sched, fraction, pool_scalars, L, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "schedule_required launch");
+}
+
+static int check_schedule_rings(const sl_level_schedule *s, const char *who) {
+    if (!s->ring || !s->count || !s->episodes || !s->pos || !s->best || !s->mean)
+        return fail(SL_E_ARG, std::string(who) + ": null ring / count / episodes / pos / best / mean");
+    return SL_OK;
+}
+
+int slhip_schedule_harvest(const sl_level_schedule *sched, const sl_step_out *out, const sl_env_scalars *scalars, int B,
+                           void *stream) {
+    if (int rc = check_schedule(sched)) return rc;
+    if (B < 1) return fail(SL_E_SHAPE, "schedule_harvest: B must be at least 1");
+    if (int rc = check_schedule_rings(sched, "schedule_harvest")) return rc;
+    if (!sched->reward_possible || !sched->cur_slot || !out || !scalars)
+        return fail(SL_E_ARG, "schedule_harvest: null reward_possible / cur_slot / out / scalars");
+    const hipError_t err = sl::launch_schedule_harvest(*sched, out, scalars, B, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "schedule_harvest launch");
+}
+
+int slhip_schedule_curriculum(const sl_level_schedule *sched, double *probs_out, void *stream) {
+    if (int rc = check_schedule(sched)) return rc;
+    if (int rc = check_schedule_rings(sched, "schedule_curriculum")) return rc;
+    if (!probs_out) return fail(SL_E_ARG, "schedule_curriculum: null probs_out");
+    const hipError_t err = sl::launch_schedule_curriculum(*sched, probs_out, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "schedule_curriculum launch");
+}
+
 }  // extern "C"

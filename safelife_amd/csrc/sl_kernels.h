@@ -109,6 +109,19 @@ hipError_t launch_replay_gather(const sl_replay &buf, const long long *index, in
 hipError_t launch_sample_actions_eps(const float *qvals, const uint8_t *active, int B, int A, double epsilon,
                                      unsigned long long seed, unsigned long long counter, int32_t *actions,
                                      hipStream_t stream);
+// sl_schedule.hip : level schedules -- the successor table's draw (host_p: the G probabilities by value, else dev_p), the
+// exit difficulty, the per-group performance rings and the curriculum's probabilities
+struct schedule_probs {
+    double p[SL_SCHEDULE_MAX_GROUPS];
+};
+hipError_t launch_schedule_draw(const sl_level_schedule &s, const schedule_probs *host_p, const double *dev_p,
+                                unsigned long long seed, unsigned long long counter, int32_t *pool_next, int L,
+                                hipStream_t stream);
+hipError_t launch_schedule_required(const sl_level_schedule &s, double fraction, sl_level_scalars *pool_scalars, int L,
+                                    hipStream_t stream);
+hipError_t launch_schedule_harvest(const sl_level_schedule &s, const sl_step_out *out, const sl_env_scalars *scalars, int B,
+                                   hipStream_t stream);
+hipError_t launch_schedule_curriculum(const sl_level_schedule &s, double *probs_out, hipStream_t stream);
 // envs [e_first, e_first + e_count) of the batch; actions / reward_t / done_t are indexed [t * tstride + e]
 // with the env's index in the whole batch
 // (sl_aql.hip dispatches the same kernel from queues of the library's own: PreparedStep below)

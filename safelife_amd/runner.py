@@ -28,6 +28,14 @@ MultiAgentDQNStep = collections.namedtuple("MultiAgentDQNStep", DQNStep._fields 
 _SPLITMIX_G = 0x9E3779B97F4A7C15        # the increment of the draw kernel's splitmix64 (slhip_sample_actions)
 
 
+def _set_training_steps(env, num_steps):
+    """An env with a level schedule (schedule.LevelSchedule) evaluates its schedules at the runner's step count, as the
+    reference's LinearSchedule reads the logger's ``training_steps``."""
+    sched = getattr(env, "level_schedule", None)
+    if sched is not None:
+        sched.training_steps = int(num_steps)
+
+
 def _model_in(obs, cast_obs):
     """What the model is handed: float32 (training/ppo.py:64, dqn.py:97), or with ``cast_obs=False`` the env's tensor as
     it is (a uint8 policy tensor stays uint8)."""
@@ -79,6 +87,7 @@ class VectorRunner(object):
         bumped (training/base_algo.py:231-238)."""
         torch = self.torch
         a = actions.to(device=self.env.device, dtype=torch.int32).contiguous()
+        _set_training_steps(self.env, self.num_steps)
         self.env.step(a)
         # what the reference's trainers see is the reward as the wrapper stack hands it on (movement bonus, exit
         # bonus, side-effect penalty: env_factory.py:277-283 wraps the env before base_algo steps it)
@@ -194,6 +203,7 @@ class DQNRunner(object):
             _hip.check(rc)
         self.draws += 1
         kept = obs.clone()
+        _set_training_steps(env, self.num_steps)
         env.step(self.actions)
         shaped = getattr(env, "shaped_reward", None)
         rewards = shaped.clone() if shaped is not None else env.reward.clone()

@@ -281,14 +281,25 @@ class SafeLifeVectorEnv(object):
                                    ``inaction_rng``: PCG64 words uint64 [B,4]).  A wrapper is active when its
                                    coefficient is not None.
                                    The wrapped float64 reward is ``env.shaped_reward`` after each step.
-                                   (MinPerformanceScheduler = ``LevelPool(min_performance_fraction=...)``.)
+                                   (MinPerformanceScheduler = ``LevelPool(min_performance_fraction=...)`` for a
+                                   constant factor, ``level_schedule=`` for one that moves with training.)
+    level_schedule : schedule.LevelSchedule or None
+                                   the reference's level iterators and exit-difficulty schedule on the device: the env
+                                   keeps a successor table of its own (``sl_env_batch.pool_next``) that one kernel redraws
+                                   before every ``step()`` -- task switching, curricula -- one kernel after the step files
+                                   the finished episodes' performances, and the pool's required points follow
+                                   ``min_performance_fraction`` (``first_level=None`` then starts the envs where the
+                                   schedule's ``first_levels`` says).  Two extra launches per step on the caller's stream,
+                                   three in curriculum mode.  Only ``step()`` and ``reset()`` drive a schedule: ``rollout()``,
+                                   ``step_async()``, ``step_slice()`` and the queue steppers raise ``ValueError``, and so
+                                   does a refreshable pool.  None: nothing changes -- no launch, no allocation.
     """
 
     def __init__(self, pool, num_envs, *, time_limit=1000, remove_white_goals=True,
                  view_shape=(15, 15), output_channels=_DEFAULT_CHANNELS, auto_reset=True,
                  first_level=None, level_stride=1, env_offset=0, with_obs=True,
                  points_on_level_exit=1, wrappers=None, slices=1, episode_streams=True, side_effects=None,
-                 policy_layout=None):
+                 policy_layout=None, level_schedule=None):
         import torch
         self.torch = torch
         if not isinstance(pool, LevelPool):
@@ -336,6 +347,14 @@ class SafeLifeVectorEnv(object):
                 raise ValueError("policy_layout must be 'uint8' or 'float32' and needs output_channels")
             self.policy_tensor = torch.zeros((B, len(chans), vw, vh), device=dev,
                                              dtype=torch.uint8 if policy_layout == "uint8" else torch.float32)
+        self.level_schedule = level_schedule
+        if level_schedule is not None:
+            if getattr(pool, "refreshable", False):
+                raise ValueError("a level schedule and a refreshable pool both own the successor table (pool_next)")
+            if level_schedule.pool is not pool:
+                raise ValueError("the level schedule was built for another pool")
+            if first_level is None:
+                first_level = level_schedule.first_levels(B, env_offset)
         if first_level is None:
             first_level = (int(env_offset) + np.arange(B)) % len(pool)
         first = np.broadcast_to(np.asarray(first_level, np.int32), (B,)).copy()
@@ -368,6 +387,8 @@ class SafeLifeVectorEnv(object):
         t["score_lut"] = torch.zeros((s.n_tables, 4096 + 65536), dtype=torch.int8, device=dev)
         if self._pool_next is not None:
             s.pool_next = self._pool_next[0].data_ptr()
+        if level_schedule is not None:      # the schedule's own table: redrawn before every step
+            s.pool_next = level_schedule._attach(self).data_ptr()
         for name in _hip.ENV_STATE_PTRS + _hip.ENV_POOL_PTRS + _hip.ENV_OUT_PTRS:
             if name == "obs":
                 s.obs = None if self.obs is None else self.obs.data_ptr()
@@ -711,10 +732,24 @@ class SafeLifeVectorEnv(object):
         if mask is not None:
             m = self.torch.as_tensor(mask, device=self.device).to(self.torch.uint8).contiguous()
         self._settle()
+        sched = self.level_schedule
+        if sched is not None:       # (envs that have played move on to a successor: drawn now, like a step's)
+            sched._before_step()
         rc = self._lib.slhip_env_reset(self._sref, _hip.ptr(m), _hip.current_stream_ptr())
         _hip.check(rc)
+        if sched is not None:
+            sched._rewind(m)
         self._caller_ahead = True
         return self.obs
+
+    _SCHEDULE_STREAMS = ("the draw, the step and the harvest are ordered on one stream; on the slice streams the table "
+                         "would change under a running step and the harvest would miss episode ends")
+    _SCHEDULE_QUEUES = ("the queue steppers run many steps on one successor table, nothing harvests their episode ends, and "
+                        "the release-free recovery replays a logged pool_next whose content has changed since")
+
+    def _no_schedule(self, what, why):
+        if self.level_schedule is not None:
+            raise ValueError("%s cannot drive a level schedule: %s (use step())" % (what, why))
 
     def _actions(self, actions, shape):
         torch = self.torch
@@ -733,8 +768,13 @@ class SafeLifeVectorEnv(object):
         # per step with two slices against 12 with one launch), so this is ONE launch on the caller's stream whatever
         # `slices` says; the slices are for step_async()
         self._settle()
+        sched = self.level_schedule
+        if sched is not None:       # draw (and required points, if due) -> the step as ever -> harvest, all on this stream
+            sched._before_step()
         rc = self._lib.slhip_env_step(self._sref, _hip.ptr(a), _hip.current_stream_ptr())
         _hip.check(rc)
+        if sched is not None:
+            sched._after_step()
         self._caller_ahead = True
         self.steps_dispatched += 1
         return self.obs, self.reward, self.done, self.info
@@ -819,6 +859,7 @@ class SafeLifeVectorEnv(object):
         state since the previous sync is not valid."""
         if self._queues is not None:
             return
+        self._no_schedule("queues_open()", self._SCHEDULE_QUEUES)
         self._rf_recover, self._rf_ckpt, self._queue_log = False, None, []
         B = self.num_envs
         n = int(slices if slices is not None else (len(queue_ids) if queue_ids is not None else
@@ -949,6 +990,7 @@ class SafeLifeVectorEnv(object):
         ``defer=True`` (``slhip_queues_stage``, at most ``_hip.QUEUES_STAGE_MAX`` steps): the steps are written --
         argument blocks, packets -- but not handed to the device until ``queues_go()``; the action buffers must exist
         now, their contents only then.  What a hipGraph's instantiate / launch split does for a stream."""
+        self._no_schedule("step_queues()", self._SCHEDULE_QUEUES)
         if isinstance(actions, int):
             ptr = actions
             if n_steps is None:
@@ -1056,6 +1098,7 @@ class SafeLifeVectorEnv(object):
         """One step per env, one launch per slice on the slice's own stream; nothing is fenced.  `actions`:
         a contiguous int32 device tensor [B] that is already complete (or ordered by ``fence()``), or its
         device address as an int.  Outputs are valid on the caller's stream after ``join()``."""
+        self._no_schedule("step_async()", self._SCHEDULE_STREAMS)
         if isinstance(actions, int):
             ptr = actions
         else:           # (a tensor: the checks step() makes through _actions(), without its conversions)
@@ -1082,6 +1125,7 @@ class SafeLifeVectorEnv(object):
         stream (``slice_stream(i)``); `actions`: the int32 device tensor [num_envs] of the whole batch (or its address) --
         only the slice's entries are read.  No fence: whoever writes the slice's actions and reads its outputs does so
         on the same stream (runner.PipelinedRunner), or orders itself against it."""
+        self._no_schedule("step_slice()", self._SCHEDULE_STREAMS)
         if not 0 <= i < self.slices or self.slices < 2:
             raise ValueError("no such slice (construct the env with slices >= 2)")
         ptr = actions if isinstance(actions, int) else actions.data_ptr()
@@ -1108,6 +1152,8 @@ class SafeLifeVectorEnv(object):
 
     def rollout(self, actions, reward_out=None, done_out=None):
         """T steps in one launch.  actions: int [T,B].  Returns (reward[T,B], done[T,B])."""
+        self._no_schedule("rollout()", "the successor table would stay constant across the launch's steps and the "
+                          "episodes that end inside it would not be harvested")
         torch = self.torch
         T = int(actions.shape[0])
         a = self._actions(actions, (T, self.num_envs))
@@ -1132,6 +1178,8 @@ class SafeLifeVectorEnv(object):
         device memory; ``None`` restores the env's own tensor.  Used by sharding.RewardGather to have
         the kernel fill a send buffer directly.  ``compact``: 8-byte records there -- reward, done, success,
         times_up: ``sl_env_batch.out_compact`` -- (the env's own tensor always takes whole records)."""
+        if out_ptr is not None:
+            self._no_schedule("set_step_outputs()", "the harvest reads the env's own step records")
         self.struct.out = self.t["out"].data_ptr() if out_ptr is None else int(out_ptr)
         self.struct.out_compact = 1 if (compact and out_ptr is not None) else 0
 
