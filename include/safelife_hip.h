@@ -1028,6 +1028,46 @@ int slhip_schedule_harvest(const sl_level_schedule *sched, const sl_step_out *ou
  * NaN or inf -> 0 and the probabilities are equal. */
 int slhip_schedule_curriculum(const sl_level_schedule *sched, double *probs_out, void *stream);
 
+/* ---- level schedules for envs with several agents (additive again: two symbols and one wrapping struct; sl_level_schedule
+ * stays as it is, 168 bytes, and SL_ABI_VERSION where it is) --------------------------------------------------------------
+ * The reference's multi-agent tasks (training/env_factory.py: asym1, curriculum-asym1) run under the same iterators and the
+ * same MinPerformanceScheduler.  The draw and the curriculum are those above, called on &m->s.  What differs is per agent:
+ * every agent has its own required points (safelife_game.py:696-714 works on arrays over the agents), and the performance a
+ * finished episode files is the AVERAGE over the env's agents (env_factory.py:91-101).
+ * s.available and s.reward_possible are not read by the two entry points below; the per-agent arrays here are. */
+typedef struct sl_level_schedule_multi { /* 208 bytes */
+    sl_level_schedule s;
+    int32_t n_agents;             /* A, 1 .. SL_MAX_AGENTS */
+    int32_t reserved;
+    const int32_t *available;        /* [L, A] initial_available_points()[a]: the agent's own table against the level's counts */
+    const int32_t *reward_possible;  /* [L, A] available + points_on_level_exit */
+    sl_level_agent *pool_agents;     /* [L, A] the env's sl_multi_agent.pool_agents (slhip_schedule_required_multi writes it) */
+    const sl_step_out *out;          /* [B, A] the env's sl_multi_agent.out (slhip_schedule_harvest_multi reads it) */
+} sl_level_schedule_multi;
+
+/* pool_agents[l][a].required_step = max(0, (int32) ceil((min_performance[l] * fraction) * (double) available[l][a])) for
+ * every slot l and agent a, one thread per pair: the two float64 products rounded one after the other, NaN and <= 0 -> 0,
+ * >= 2^31 - 1 -> INT32_MAX, exactly as slhip_schedule_required.  Nothing else of a record is touched (required_reset is the
+ * level's own min_performance).  The multi-agent step copies required_step into the agent's state when the env reloads, so
+ * an env picks the new value up at its next reload.  fraction must be finite.
+ * Needs of *m: s.L, s.min_performance, n_agents, available, pool_agents. */
+int slhip_schedule_required_multi(const sl_level_schedule_multi *m, double fraction, void *stream);
+
+/* slhip_schedule_harvest for records [B, A].  Env e has finished on this step when ALL of out[e][0 .. A) have done != 0 --
+ * the step on which the multi-agent kernel reloads it; an agent that left earlier keeps done = 1 and its episode_reward in
+ * `out` on every later step, so an episode whose agents finish on different steps files exactly one record, on the last of
+ * them, and an env with only some agents done files nothing.  For every finished env, in ascending e, with slot =
+ * cur_slot[e]:
+ *   q[a] = f64(out[e][a].episode_reward) / f64(reward_possible[slot][a]);
+ *   sum  = np.add.reduce(q): 0.0 + (q[0] + q[1] + ... in index order) for A < 8, and for A = 8 numpy's eight accumulators
+ *          0.0 + (((q0 + q1) + (q2 + q3)) + ((q4 + q5) + (q6 + q7)));
+ *   perf = sum / f64(A); 0.0 when THAT is NaN or +-inf (the reference tests the average, not each quotient).
+ * Everything else -- the ring, count / pos / episodes / best / mean, slots outside every group, cur_slot[e] =
+ * scalars[e].level_idx for every env, the placing by the done flags alone -- is slhip_schedule_harvest's.  Records of envs
+ * that have not finished are not read beyond their done bytes.  One launch.
+ * Needs of *m: s (groups, rings, cur_slot), n_agents, reward_possible, out. */
+int slhip_schedule_harvest_multi(const sl_level_schedule_multi *m, const sl_env_scalars *scalars, int B, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,7 @@ EXPORTS = (
     "slhip_sample_actions_masked", "slhip_rollout_record_multi", "slhip_training_batch_multi",
     "slhip_rollout_compact_chunks", "slhip_rollout_compact", "slhip_rollout_gather",
     "slhip_schedule_draw", "slhip_schedule_required", "slhip_schedule_harvest", "slhip_schedule_curriculum",
+    "slhip_schedule_required_multi", "slhip_schedule_harvest_multi",
 )
 SCHEDULE_MAX_GROUPS, SCHEDULE_MAX_LOOKBACK = 8, 1024
 SCHEDULE_BAD_PROBS = 1
@@ -183,6 +184,12 @@ class LevelSchedule(C.Structure):
                                              "episodes", "pos", "best", "mean", "status")])
 
 
+class LevelScheduleMulti(C.Structure):
+    """struct sl_level_schedule_multi (208 bytes)"""
+    _fields_ = ([("s", LevelSchedule), ("n_agents", C.c_int32), ("reserved", C.c_int32)]
+                + [(n, C.c_void_p) for n in ("available", "reward_possible", "pool_agents", "out")])
+
+
 class EnvBatch(C.Structure):
     _fields_ = (
         [(n, C.c_int32) for n in ENV_SCALARS_HEAD]
@@ -296,6 +303,8 @@ def lib():
         L.slhip_schedule_required.argtypes = [C.POINTER(LevelSchedule), C.c_double, _p, C.c_int, _p]
         L.slhip_schedule_harvest.argtypes = [C.POINTER(LevelSchedule), _p, _p, C.c_int, _p]
         L.slhip_schedule_curriculum.argtypes = [C.POINTER(LevelSchedule), _p, _p]
+        L.slhip_schedule_required_multi.argtypes = [C.POINTER(LevelScheduleMulti), C.c_double, _p]
+        L.slhip_schedule_harvest_multi.argtypes = [C.POINTER(LevelScheduleMulti), _p, C.c_int, _p]
         L.slhip_obs_to_policy.argtypes = [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]
         L.slhip_gather_unique_id.argtypes = [_p]
         L.slhip_gather_init.argtypes = [_p, C.c_int, C.c_int, C.POINTER(_p)]

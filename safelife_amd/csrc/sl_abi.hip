@@ -1918,4 +1918,30 @@ int slhip_schedule_curriculum(const sl_level_schedule *sched, double *probs_out,
     return err == hipSuccess ? SL_OK : hip_fail(err, "schedule_curriculum launch");
 }
 
+int slhip_schedule_required_multi(const sl_level_schedule_multi *m, double fraction, void *stream) {
+    if (!m) return fail(SL_E_ARG, "schedule_required_multi: null schedule description");
+    if (m->s.L < 1) return fail(SL_E_SHAPE, "schedule_required_multi: L must be at least 1");
+    if (m->n_agents < 1 || m->n_agents > SL_MAX_AGENTS)
+        return fail(SL_E_SHAPE, "schedule_required_multi: n_agents outside 1..SL_MAX_AGENTS");
+    if ((long long)m->s.L * m->n_agents > 2147483647ll) return fail(SL_E_SHAPE, "schedule_required_multi: L * n_agents overflows");
+    if (!(fraction - fraction == 0.0)) return fail(SL_E_SHAPE, "schedule_required_multi: fraction is not finite");
+    if (!m->s.min_performance || !m->available || !m->pool_agents)
+        return fail(SL_E_ARG, "schedule_required_multi: null min_performance / available / pool_agents");
+    const hipError_t err = sl::launch_schedule_required_multi(*m, fraction, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "schedule_required_multi launch");
+}
+
+int slhip_schedule_harvest_multi(const sl_level_schedule_multi *m, const sl_env_scalars *scalars, int B, void *stream) {
+    if (!m) return fail(SL_E_ARG, "schedule: null schedule description");
+    if (int rc = check_schedule(&m->s)) return rc;
+    if (B < 1) return fail(SL_E_SHAPE, "schedule_harvest_multi: B must be at least 1");
+    if (m->n_agents < 1 || m->n_agents > SL_MAX_AGENTS)
+        return fail(SL_E_SHAPE, "schedule_harvest_multi: n_agents outside 1..SL_MAX_AGENTS");
+    if (int rc = check_schedule_rings(&m->s, "schedule_harvest_multi")) return rc;
+    if (!m->reward_possible || !m->s.cur_slot || !m->out || !scalars)
+        return fail(SL_E_ARG, "schedule_harvest_multi: null reward_possible / cur_slot / out / scalars");
+    const hipError_t err = sl::launch_schedule_harvest_multi(*m, scalars, B, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "schedule_harvest_multi launch");
+}
+
 }  // extern "C"

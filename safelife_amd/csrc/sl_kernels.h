@@ -122,6 +122,11 @@ hipError_t launch_schedule_required(const sl_level_schedule &s, double fraction,
 hipError_t launch_schedule_harvest(const sl_level_schedule &s, const sl_step_out *out, const sl_env_scalars *scalars, int B,
                                    hipStream_t stream);
 hipError_t launch_schedule_curriculum(const sl_level_schedule &s, double *probs_out, hipStream_t stream);
+// the same for envs with m.n_agents agents: per-agent required points into m.pool_agents, one record per env whose agents
+// are all done from m.out
+hipError_t launch_schedule_required_multi(const sl_level_schedule_multi &m, double fraction, hipStream_t stream);
+hipError_t launch_schedule_harvest_multi(const sl_level_schedule_multi &m, const sl_env_scalars *scalars, int B,
+                                         hipStream_t stream);
 // envs [e_first, e_first + e_count) of the batch; actions / reward_t / done_t are indexed [t * tstride + e]
 // with the env's index in the whole batch
 // (sl_aql.hip dispatches the same kernel from queues of the library's own: PreparedStep below)

@@ -15,6 +15,14 @@
 //                          env order, and every env's current slot is noted for the next call
 //   k_schedule_curriculum  the softmax over the rings' least-squares slopes (get_next_parameters) -> G probabilities
 //
+// Envs with A agents (sl_level_schedule_multi) share the draw and the curriculum and have their own two:
+//
+//   k_schedule_required_multi  one lane per (slot, agent): pool_agents[l][a].required_step from the agent's own available
+//                              points
+//   k_schedule_harvest_multi   the harvest below with "done" read as ALL A agents of the env done (the step on which the env
+//                              reloads) and the performance the average of the A agents' quotients, summed as np.average
+//                              sums them (env_factory.py:91-101)
+//
 // Nothing is fused (the library is built with -ffp-contract=off; the pragma says it again), so everything but exp() is the
 // arithmetic the host model spells out, bit for bit.
 //
@@ -26,7 +34,8 @@
 // out[e].done, which nobody writes, so no workgroup reads what another one writes.  Finished episodes are few (about 8
 // of 8192 per step), so workgroup 0's time is its staging loads and 2 * G barriers.  (A first version gave every lane
 // ceil(B / 256) consecutive envs to read straight from global memory: 32 dependent round trips per lane at 8192 envs,
-// 21 us per call.)
+// 21 us per call.)  The multi-agent harvest is the same code: the staged byte is the AND of the env's A done flags (A
+// independent loads per lane, 16 A bytes per env), and workgroups 1 .. decide "did not finish" by the same AND of `out`.
 #include "sl_kernels.h"
 
 #pragma clang fp contract(off)
@@ -109,6 +118,22 @@ __global__ __launch_bounds__(SCHED_THREADS) void k_schedule_required(const doubl
     pool_scalars[l].required_step = r;
 }
 
+__global__ __launch_bounds__(SCHED_THREADS) void k_schedule_required_multi(const double *__restrict__ min_performance,
+                                                                           const int32_t *__restrict__ available,
+                                                                           double fraction,
+                                                                           sl_level_agent *__restrict__ pool_agents, int A,
+                                                                           int n) {
+    const int i = blockIdx.x * SCHED_THREADS + threadIdx.x;     // slot i / A, agent i % A
+    if (i >= n) return;
+    const double c = ceil(__dmul_rn(__dmul_rn(min_performance[i / A], fraction), (double)available[i]));
+    int32_t r = 0;                                      // NaN and everything <= 0
+    if (c >= 2147483647.0)
+        r = 2147483647;
+    else if (c > 0.0)
+        r = (int32_t)c;
+    pool_agents[i].required_step = r;
+}
+
 // the ring's records, oldest first, into LDS: n = min(count, lookback) of them
 __device__ __forceinline__ int ring_to_lds(const sl_level_schedule &s, int g, long long count, int pos, double *lds) {
     const int n = count < s.lookback ? (int)max(count, 0ll) : s.lookback;
@@ -138,11 +163,46 @@ __device__ __forceinline__ double sum_in_order(const double *lds, int m, W w) {
     return sum;
 }
 
-__global__ __launch_bounds__(SCHED_THREADS) void k_schedule_harvest(sl_level_schedule s, const sl_step_out *__restrict__ out,
-                                                                    const sl_env_scalars *__restrict__ scalars, int B) {
+// has env e finished: its record's done flag; with A agents, all A of them (the step on which the env reloads)
+template <bool MULTI>
+__device__ __forceinline__ bool env_done(const sl_step_out *__restrict__ out, int e, int A) {
+    if (!MULTI) return out[e].done != 0;
+    const sl_step_out *rec = out + (long long)e * A;
+    bool d = true;
+#pragma unroll
+    for (int a = 0; a < SL_MAX_AGENTS; ++a)             // (independent loads)
+        if (a < A) d &= rec[a].done != 0;
+    return d;
+}
+
+// np.average(reward / reward_possible) over the env's A agents (env_factory.py:95): float64 quotients, np.add.reduce -- the
+// identity 0.0 plus the sum in index order for fewer than 8 elements, plus numpy's eight-accumulator tree for exactly 8 --
+// divided by A once
+__device__ __forceinline__ double performance_multi(const sl_step_out *__restrict__ rec, const int32_t *__restrict__ possible,
+                                                    int A) {
+    double q[SL_MAX_AGENTS];
+#pragma unroll
+    for (int a = 0; a < SL_MAX_AGENTS; ++a) q[a] = a < A ? (double)rec[a].episode_reward / (double)possible[a] : 0.0;
+    double sum;
+    if (A == SL_MAX_AGENTS) {
+        sum = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
+    } else {
+        sum = q[0];
+#pragma unroll
+        for (int a = 1; a < SL_MAX_AGENTS - 1; ++a)
+            if (a < A) sum += q[a];
+    }
+    return (0.0 + sum) / (double)A;                     // (0.0 + -0.0 is +0.0, as numpy's is)
+}
+
+// MULTI: out is [B, A] and reward_possible [L, A]; else A is 1
+template <bool MULTI>
+__device__ __forceinline__ void harvest(const sl_level_schedule &s, const int32_t *__restrict__ reward_possible,
+                                        const sl_step_out *__restrict__ out, const sl_env_scalars *__restrict__ scalars,
+                                        int B, int A) {
     if (blockIdx.x > 0) {       // the envs that go on
         const int e = (blockIdx.x - 1) * SCHED_THREADS + threadIdx.x;
-        if (e < B && !out[e].done) s.cur_slot[e] = scalars[e].level_idx;
+        if (e < B && !env_done<MULTI>(out, e, A)) s.cur_slot[e] = scalars[e].level_idx;
         return;
     }
     __shared__ int wave_sum[SCHED_THREADS / 64];
@@ -158,7 +218,7 @@ __global__ __launch_bounds__(SCHED_THREADS) void k_schedule_harvest(sl_level_sch
         const int nt = min(HARVEST_TILE, B - tile);
         __syncthreads();                                // (the previous tile's flags have been read)
 #pragma unroll 8
-        for (int i = threadIdx.x; i < nt; i += SCHED_THREADS) flag[i] = out[tile + i].done ? 1 : 0;
+        for (int i = threadIdx.x; i < nt; i += SCHED_THREADS) flag[i] = env_done<MULTI>(out, tile + i, A) ? 1 : 0;
         for (int i = nt + threadIdx.x; i < ((nt + 63) & ~63); i += SCHED_THREADS) flag[i] = 0;
         __syncthreads();
         const int lo = threadIdx.x * HARVEST_PER_LANE;
@@ -187,7 +247,11 @@ __global__ __launch_bounds__(SCHED_THREADS) void k_schedule_harvest(sl_level_sch
             const int g = group_of(s, slot);
             s.cur_slot[e] = scalars[e].level_idx;
             if (g < 0) continue;                        // a slot outside every group: no record
-            double perf = (double)out[e].episode_reward / (double)s.reward_possible[slot];
+            double perf;
+            if (MULTI)
+                perf = performance_multi(out + (long long)e * A, reward_possible + (long long)slot * A, A);
+            else
+                perf = (double)out[e].episode_reward / (double)reward_possible[slot];
             if (!(perf - perf == 0.0)) perf = 0.0;      // NaN, +-inf
             int r = 0, n = 0, at = 0;
 #pragma unroll
@@ -224,6 +288,19 @@ __global__ __launch_bounds__(SCHED_THREADS) void k_schedule_harvest(sl_level_sch
             s.pos[g] = pos;
         }
     }
+}
+
+__global__ __launch_bounds__(SCHED_THREADS) void k_schedule_harvest(sl_level_schedule s, const sl_step_out *__restrict__ out,
+                                                                    const sl_env_scalars *__restrict__ scalars, int B) {
+    harvest<false>(s, s.reward_possible, out, scalars, B, 1);
+}
+
+__global__ __launch_bounds__(SCHED_THREADS) void k_schedule_harvest_multi(sl_level_schedule s,
+                                                                          const int32_t *__restrict__ reward_possible,
+                                                                          const sl_step_out *__restrict__ out,
+                                                                          const sl_env_scalars *__restrict__ scalars, int B,
+                                                                          int A) {
+    harvest<true>(s, reward_possible, out, scalars, B, A);
 }
 
 // get_next_parameters (env_factory.py:111-127) in float64, one workgroup:
@@ -295,6 +372,20 @@ hipError_t launch_schedule_harvest(const sl_level_schedule &s, const sl_step_out
                                    hipStream_t stream) {
     hipLaunchKernelGGL(k_schedule_harvest, dim3(1 + (B + SCHED_THREADS - 1) / SCHED_THREADS), dim3(SCHED_THREADS), 0, stream,
                        s, out, scalars, B);
+    return hipGetLastError();
+}
+
+hipError_t launch_schedule_required_multi(const sl_level_schedule_multi &m, double fraction, hipStream_t stream) {
+    const int n = m.s.L * m.n_agents;
+    hipLaunchKernelGGL(k_schedule_required_multi, dim3((n + SCHED_THREADS - 1) / SCHED_THREADS), dim3(SCHED_THREADS), 0, stream,
+                       m.s.min_performance, m.available, fraction, m.pool_agents, m.n_agents, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_schedule_harvest_multi(const sl_level_schedule_multi &m, const sl_env_scalars *scalars, int B,
+                                         hipStream_t stream) {
+    hipLaunchKernelGGL(k_schedule_harvest_multi, dim3(1 + (B + SCHED_THREADS - 1) / SCHED_THREADS), dim3(SCHED_THREADS), 0,
+                       stream, m.s, m.reward_possible, m.out, scalars, B, m.n_agents);
     return hipGetLastError();
 }
 

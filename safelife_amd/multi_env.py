@@ -33,6 +33,12 @@ class SafeLifeMultiAgentVectorEnv(object):
         ``policy_tensor``  [B, A, C, view_w, view_h] uint8 / float32
         ``side_effects_flush()``: a ``SideEffectBatch`` with one entry per env EPISODE (queued on the step where every
                            agent is done), whose ``agent_records()`` hold every agent's record of that step
+    level_schedule : schedule.LevelSchedule (built on this pool) or None
+        the reference's level iterators and exit-difficulty schedule on the device, as for SafeLifeVectorEnv: the env's
+        first levels are the schedule's ``first_levels`` (unless ``first_level`` is given), every reload takes its successor
+        from the schedule's table, an episode files one performance record -- the average over the env's agents, on the
+        step where the last of them finishes -- and every agent's required points follow ``min_performance_fraction``.
+        Two extra launches per step on the caller's stream, three in curriculum mode.
 
     ``reset()`` -> obs;  ``step(actions)`` -> (obs, reward, done, info) with
         actions  int   [B, A]   0..8 (an agent that is done takes 0: training/base_algo.py:216-219)
@@ -47,13 +53,17 @@ class SafeLifeMultiAgentVectorEnv(object):
     def __init__(self, pool, num_envs, *, time_limit=1000, remove_white_goals=True, view_shape=(15, 15),
                  output_channels=tuple(range(16)) + (25, 26, 27), auto_reset=True, first_level=None, level_stride=1,
                  env_offset=0, with_obs=True, points_on_level_exit=1, episode_streams=True, wrappers=None,
-                 side_effects=None, policy_layout=None):
+                 side_effects=None, policy_layout=None, level_schedule=None):
         import torch
         if not isinstance(pool, LevelPool) or getattr(pool, "n_agents", 1) < 1:
             raise TypeError("pool must be a LevelPool")
         A = int(pool.n_agents)
         if A > _hip.SL_MAX_AGENTS:
             raise ValueError("at most %d agents per board" % _hip.SL_MAX_AGENTS)
+        if level_schedule is not None:
+            level_schedule._check_env(pool, A)
+            if first_level is None:
+                first_level = level_schedule.first_levels(num_envs, env_offset)
         # the boards, goals, generators, exit tables, the pool and the view are the single-agent env's: built once there
         self.base = base = SafeLifeVectorEnv(pool, num_envs, time_limit=time_limit, remove_white_goals=remove_white_goals,
                                              view_shape=view_shape, output_channels=output_channels, auto_reset=auto_reset,
@@ -103,6 +113,11 @@ class SafeLifeMultiAgentVectorEnv(object):
         self._x = None
         if wrappers or side_effects or policy_layout is not None:
             self._setup_extras(wrappers, side_effects, policy_layout)
+        self.level_schedule = level_schedule
+        if level_schedule is not None:      # the schedule's own successor table: redrawn before every step
+            base.struct.pool_next = level_schedule._attach(self).data_ptr()
+            # (the base env's sliced and queue steppers and its rollout() refuse to run under a schedule)
+            base.level_schedule = level_schedule
 
     def _setup_extras(self, wrappers, side_effects, policy_layout):
         torch, t, base, dev = self.torch, self.t, self.base, self.device
@@ -151,10 +166,15 @@ class SafeLifeMultiAgentVectorEnv(object):
         if mask is not None:
             mk = self.torch.as_tensor(np.ascontiguousarray(mask, dtype=np.uint8)).to(self.device)
         mp = None if mk is None else mk.data_ptr()
+        sched = self.level_schedule
+        if sched is not None:       # (envs that have played move on to a successor: drawn now, like a step's)
+            sched._before_step()
         if self._x is not None:
             _hip.check(self._lib.slhip_env_reset_multi_ex(self.base._sref, self._mref, self._x, mp, _hip.current_stream_ptr()))
         else:
             _hip.check(self._lib.slhip_env_reset_multi(self.base._sref, self._mref, mp, _hip.current_stream_ptr()))
+        if sched is not None:
+            sched._rewind(mk)
         if mk is not None:
             self.torch.cuda.current_stream().synchronize()      # (the mask tensor is the call's own)
         return self.obs
@@ -165,11 +185,16 @@ class SafeLifeMultiAgentVectorEnv(object):
         if tuple(a.shape) != (self.num_envs, self.n_agents):
             raise ValueError("actions must have shape [num_envs, n_agents]")
         self._actions = a                                       # (alive until the next step)
+        sched = self.level_schedule
+        if sched is not None:       # draw (and required points, if due) -> the step as ever -> harvest, all on this stream
+            sched._before_step()
         if self._x is not None:
             _hip.check(self._lib.slhip_env_step_multi_ex(self.base._sref, self._mref, self._x, a.data_ptr(),
                                                          _hip.current_stream_ptr()))
         else:
             _hip.check(self._lib.slhip_env_step_multi(self.base._sref, self._mref, a.data_ptr(), _hip.current_stream_ptr()))
+        if sched is not None:
+            sched._after_step()
         self.base.steps_dispatched += 1
         return self.obs, self.reward, self.done, self.info
 

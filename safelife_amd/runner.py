@@ -404,6 +404,7 @@ class MultiAgentRunner(object):
             _hip.check(rc)
         self.draws += 1
         kept = obs.clone()
+        _set_training_steps(env, self.num_steps)
         env.step(self.actions)
         rewards = (env.shaped_reward if env.shaped_reward is not None else env.reward).clone()
         done = env.done.to(torch.bool)
@@ -536,6 +537,7 @@ class MultiAgentDQNRunner(object):
             _hip.check(rc)
         self.draws += 1
         kept = obs.clone()
+        _set_training_steps(env, self.num_steps)
         env.step(self.actions)
         rewards = (env.shaped_reward if env.shaped_reward is not None else env.reward).clone()
         done = env.done.to(torch.bool)

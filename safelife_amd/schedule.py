@@ -10,11 +10,16 @@ The reference's trainers do not cycle a fixed list of levels (training/env_facto
 * ``curriculum-append-spawn`` and the ``asym1`` tasks pick the family by a softmax over the recent slope of performance
   (``CurricularLevelIterator``, :51-146).
 
-``LevelSchedule`` does the same for a ``SafeLifeVectorEnv`` without a host visit per reset.  The pool is a large
+``LevelSchedule`` does the same for a ``SafeLifeVectorEnv`` or a ``SafeLifeMultiAgentVectorEnv`` without a host visit per
+reset.  The pool is a large
 pre-generated library that stays resident, cut into *groups* (families: contiguous slot ranges).  Before every step one
 kernel redraws the successor table the step kernels read (``sl_env_batch.pool_next``), after every step one kernel files the
 finished episodes' performances into their group's ring, and when the exit-difficulty schedule moves one kernel rewrites
 ``pool_scalars[l].required_step``.  The step kernels themselves are untouched.
+
+With several agents per env (the reference's ``asym1`` / ``curriculum-asym1`` tasks) every agent has its own required points
+-- ``pool_agents[l][a].required_step``, from the agent's own points table -- and an episode files ONE record, on the step
+where the env's last agent finishes: the average over the agents of reward / reward_possible (env_factory.py:91-101).
 
 One difference to the reference, by construction: the draw is per SLOT and step, not per env.  Two envs whose episodes
 end on the same slot in the same step load the same successor (their random streams still differ through the env's
@@ -120,7 +125,8 @@ def _check_probs(p, G):
 
 class LevelSchedule(object):
     """
-    pool : LevelPool            single-agent, not refreshable: slots are never rewritten
+    pool : LevelPool            not refreshable: slots are never rewritten; ``LevelPool(levels, n_agents=A)`` for the
+                                multi-agent env
     groups : [(start, len), ...] or [range, ...]
                                 1..8 disjoint slot ranges of at least one slot; slots outside every group are never drawn
     mode : "uniform"            equal group probabilities (the reference's curriculum "uniform" as well)
@@ -135,7 +141,11 @@ class LevelSchedule(object):
     lookback : int              records per group the curriculum looks at (the reference: 100)
 
     ``training_steps`` is the argument of the callables; the driver sets it (the runners do, from their ``num_steps``).
-    Attach with ``SafeLifeVectorEnv(pool, ..., level_schedule=schedule)``; a schedule serves one env.
+    Attach with ``SafeLifeVectorEnv(pool, ..., level_schedule=schedule)`` or, for a pool with ``n_agents`` agents,
+    ``SafeLifeMultiAgentVectorEnv(pool, ..., level_schedule=schedule)``; a schedule serves one env.
+
+    ``available``: the points each level offers, int32 ``[L]`` -- ``[L, A]`` for a pool with A > 1 agents, every agent's own
+    table against the level's counts.
     """
 
     MODES = ("uniform", "switching", "curriculum")
@@ -147,9 +157,7 @@ class LevelSchedule(object):
         if pool.refreshable:
             raise ValueError("a level schedule and a refreshable pool both own the successor table (pool_next): "
                              "build the pool without refreshable=True")
-        if pool.n_agents > 1:
-            raise ValueError("level schedules are single-agent (the per-agent required points of multi-agent pools are "
-                             "not rewritten)")
+        self.n_agents = int(pool.n_agents)
         self.pool = pool
         L = pool.n_slots
         gs = []
@@ -191,10 +199,16 @@ class LevelSchedule(object):
         self.training_steps = 0
         # per slot: the level's own min_performance and agent 0's available points (safelife_game.py:696-709)
         self.min_performance = np.array([lv.min_performance for lv in pool.levels], np.float64)
-        self.available = np.zeros(L, np.int32)
+        self.available = np.zeros(L if self.n_agents == 1 else (L, self.n_agents), np.int32)
         for k, lv in enumerate(pool.levels):
-            table = pool.points_table[pool.pool_table_idx[k]].astype(np.int64)
-            self.available[k] = available_points(table, pool.initial_counts[k], initial_colors(lv.board))
+            colors = initial_colors(lv.board)
+            if self.n_agents == 1:
+                table = pool.points_table[pool.pool_table_idx[k]].astype(np.int64)
+                self.available[k] = available_points(table, pool.initial_counts[k], colors)
+                continue
+            for a in range(self.n_agents):      # the agent's own table against the level's counts, as LevelPool's
+                table = pool.points_table[pool.pool_agent_table_idx[k, a]].astype(np.int64)
+                self.available[k, a] = available_points(table, pool.initial_counts[k], colors)
         self.env = None
         self.draws = 0
         self._fraction_sent = None
@@ -245,22 +259,41 @@ class LevelSchedule(object):
         index = int(env_offset) + np.arange(int(num_envs), dtype=np.int64)
         return draw_model(self.groups, _check_probs(p, len(self.groups)), self.seed, FIRST_LEVELS_COUNTER, index)
 
-    # ---- device side (SafeLifeVectorEnv calls these)
+    def reward_possible(self, points_on_level_exit=1):
+        """What the logger records as ``reward_possible`` (safelife_logger.py:286-287): ``available`` plus the exit's
+        points, int32 in the shape of ``available``."""
+        return (self.available.astype(np.int64) + int(points_on_level_exit)).astype(np.int32)
+
+    # ---- device side (SafeLifeVectorEnv and SafeLifeMultiAgentVectorEnv call these)
+
+    def _check_env(self, pool, n_agents):
+        """Raises unless this schedule can serve an env on `pool` with `n_agents` agents per board (None: a
+        SafeLifeVectorEnv)."""
+        if n_agents is None:
+            if self.n_agents > 1:
+                raise ValueError("this level schedule was built on a pool with %d agents per level: it serves a "
+                                 "SafeLifeMultiAgentVectorEnv, not a single-agent SafeLifeVectorEnv" % self.n_agents)
+        elif int(n_agents) != self.n_agents:
+            raise ValueError("this level schedule was built on a pool with %d agent%s per level and cannot serve a "
+                             "multi-agent env with %d" % (self.n_agents, "" if self.n_agents == 1 else "s", n_agents))
+        if pool is not self.pool:
+            raise ValueError("the schedule was built for another pool")
 
     def _attach(self, env):
         if self.env is not None:
             raise ValueError("this LevelSchedule already serves an env")
-        if env.pool is not self.pool:
-            raise ValueError("the schedule was built for another pool")
+        # a SafeLifeMultiAgentVectorEnv keeps the boards, the scalars and the pool in its single-agent base env
+        multi = getattr(env, "n_agents", None) is not None
+        base = env.base if multi else env
+        self._check_env(env.pool, env.n_agents if multi else None)
         torch, dev = env.torch, env.device
-        self.env = env
+        self.env, self._base, self._multi = env, base, multi
         G, n, L, B = len(self.groups), self.lookback, self.pool.n_slots, env.num_envs
         t = self.t = {}
         t["min_performance"] = torch.from_numpy(self.min_performance).to(dev)
         t["available"] = torch.from_numpy(self.available).to(dev)
-        possible = self.available.astype(np.int64) + int(env.struct.exit_points)
-        t["reward_possible"] = torch.from_numpy(possible.astype(np.int32)).to(dev)
-        t["cur_slot"] = env.t["scalars"][:, _hip.SCALAR_COLS["level_idx"]].clone()
+        t["reward_possible"] = torch.from_numpy(self.reward_possible(base.struct.exit_points)).to(dev)
+        t["cur_slot"] = base.t["scalars"][:, _hip.SCALAR_COLS["level_idx"]].clone()
         t["ring"] = torch.zeros((G, n), dtype=torch.float64, device=dev)
         t["count"] = torch.ones(G, dtype=torch.int64, device=dev)
         t["episodes"] = torch.zeros(G, dtype=torch.int64, device=dev)
@@ -270,17 +303,26 @@ class LevelSchedule(object):
         t["status"] = torch.zeros(1, dtype=torch.int32, device=dev)
         t["probs"] = torch.full((G,), 1.0 / G, dtype=torch.float64, device=dev)
         t["pool_next"] = torch.arange(L, dtype=torch.int32, device=dev)
-        s = self.struct = _hip.LevelSchedule()
+        if multi:       # the per-agent arrays [L, A] travel in the wrapping struct (the inner two pointers stay null)
+            m = self._mstruct = _hip.LevelScheduleMulti()
+            m.n_agents = self.n_agents
+            m.available, m.reward_possible = t["available"].data_ptr(), t["reward_possible"].data_ptr()
+            m.pool_agents, m.out = env.t["pool_agents"].data_ptr(), env.t["out"].data_ptr()
+            s = self.struct = m.s
+            self._mref = C.byref(m)
+            per_slot = ("min_performance",)
+        else:
+            s = self.struct = _hip.LevelSchedule()
+            per_slot = ("min_performance", "available", "reward_possible")
         s.G, s.lookback, s.L = G, n, L
-        for g, (start, m) in enumerate(self.groups):
-            s.start[g], s.len[g] = start, m
-        for name in ("min_performance", "available", "reward_possible", "cur_slot", "ring", "count", "episodes", "pos",
-                     "best", "mean", "status"):
+        for g, (start, length) in enumerate(self.groups):
+            s.start[g], s.len[g] = start, length
+        for name in per_slot + ("cur_slot", "ring", "count", "episodes", "pos", "best", "mean", "status"):
             setattr(s, name, t[name].data_ptr())
         self._sref = C.byref(s)
         self._lib = _hip.lib()
         # shards of one run draw different tables: the seed carries the global index of env 0, as DQNRunner's does
-        self._kernel_seed = (self.seed + _G64 * int(env.env_offset)) & _MASK
+        self._kernel_seed = (self.seed + _G64 * int(base.env_offset)) & _MASK
         self._on_device = self.mode == "curriculum" and self.curriculum == "progress_estimate"
         self.draws = 0
         self._fraction_sent = None
@@ -288,7 +330,7 @@ class LevelSchedule(object):
 
     def _rewind(self, mask=None):
         """After the envs (those with mask != 0) have been reset from outside the step: their episodes start over."""
-        now = self.env.t["scalars"][:, _hip.SCALAR_COLS["level_idx"]]
+        now = self._base.t["scalars"][:, _hip.SCALAR_COLS["level_idx"]]
         if mask is None:
             self.t["cur_slot"].copy_(now)
         else:
@@ -300,7 +342,10 @@ class LevelSchedule(object):
         L = self.pool.n_slots
         f = self.fraction()
         if f is not None and f != self._fraction_sent:
-            _hip.check(lib.slhip_schedule_required(self._sref, f, _hip.ptr(self.env.t["pool_scalars"]), L, st))
+            if self._multi:
+                _hip.check(lib.slhip_schedule_required_multi(self._mref, f, st))
+            else:
+                _hip.check(lib.slhip_schedule_required(self._sref, f, _hip.ptr(self.env.t["pool_scalars"]), L, st))
             self._fraction_sent = f
         if self._on_device:
             _hip.check(lib.slhip_schedule_curriculum(self._sref, _hip.ptr(self.t["probs"]), st))
@@ -316,8 +361,12 @@ class LevelSchedule(object):
 
     def _after_step(self):
         env = self.env
-        rc = self._lib.slhip_schedule_harvest(self._sref, _hip.ptr(env.t["out"]), _hip.ptr(env.t["scalars"]), env.num_envs,
-                                              _hip.current_stream_ptr())
+        if self._multi:
+            rc = self._lib.slhip_schedule_harvest_multi(self._mref, _hip.ptr(self._base.t["scalars"]), env.num_envs,
+                                                        _hip.current_stream_ptr())
+        else:
+            rc = self._lib.slhip_schedule_harvest(self._sref, _hip.ptr(env.t["out"]), _hip.ptr(env.t["scalars"]),
+                                                  env.num_envs, _hip.current_stream_ptr())
         if rc:
             _hip.check(rc)
 

@@ -305,6 +305,8 @@ class SafeLifeVectorEnv(object):
         if not isinstance(pool, LevelPool):
             raise TypeError("pool must be a LevelPool")
         self.pool = pool
+        if level_schedule is not None and level_schedule.n_agents > 1:      # (refused before anything is allocated)
+            level_schedule._check_env(pool, None)
         self.device = _hip.device()
         self.num_envs = B = int(num_envs)
         self.env_offset = int(env_offset)
