@@ -160,8 +160,10 @@ class MultiAgentRolloutBuffer(_Window):
     """
     A window of ``MultiAgentRunner`` steps: ``[T, B * A]`` columns, column ``b * A + a`` being agent ``a`` of env ``b``,
     with ``active`` uint8 ``[T, B * A]`` next to the arrays of ``RolloutBuffer``.  The state the reference carries from
-    step to step -- and from window to window -- lives here too: ``active_now`` uint8 ``[B, A]`` (its ``~last_done``) and
-    ``num_resets`` int64 ``[B]``; ``record`` moves both on (``slhip_rollout_record_multi``, one launch).
+    step to step -- and from window to window -- is ``active_now`` uint8 ``[B, A]`` (its ``~last_done``) and
+    ``num_resets`` int64 ``[B]``; ``record`` moves both on (``slhip_rollout_record_multi``, one launch).  Every buffer
+    has a pair of its own, for whoever records windows by hand; a runner, whose windows come and go, keeps the pair of
+    a one-step buffer for its whole life and names it to ``record``.
 
     Parameters
     ----------
@@ -198,16 +200,20 @@ class MultiAgentRolloutBuffer(_Window):
         self._scan = torch.zeros(self._lib.slhip_rollout_compact_chunks(self._sref), dtype=torch.int32, device=dev)
         self.rows = self.agent_ids = None
 
-    def record(self, t, step):
+    def record(self, t, step, state=None):
         """Row ``t`` of the window from a step of all ``B * A`` agents (an object with obs, actions, rewards, done,
         policies, values shaped ``[B, A, ...]`` or ``[B * A, ...]``).  What ``active_now`` says decides which columns are
         kept -- the others record zeros, whatever the step holds for them -- and then ``active_now`` / ``num_resets``
-        move on to the next step.  The observation goes with ``copy_``, everything else with one kernel."""
+        move on to the next step.  They are those of ``state``, another ``MultiAgentRolloutBuffer`` of the same B and A,
+        or the window's own.  The observation goes with ``copy_``, everything else with one kernel."""
+        state = self if state is None else state
+        if state.active_now.shape != self.active_now.shape:
+            raise ValueError("state is for another number of envs or agents")
         tensors = self._step_tensors(t, step, self.columns)
         if self.obs is not None:
             self.obs[t].copy_(step.obs.reshape(self.obs.shape[1:]))
-        self.resets_at[t].copy_(self.num_resets)
-        self._record(self._lib.slhip_rollout_record_multi, t, tensors, _hip.ptr(self.active_now), _hip.ptr(self.num_resets))
+        self.resets_at[t].copy_(state.num_resets)
+        self._record(self._lib.slhip_rollout_record_multi, t, tensors, _hip.ptr(state.active_now), _hip.ptr(state.num_resets))
 
     def finish(self, final_values, gamma=0.97, lmda=0.95, gather_obs=True, dense=False):
         """Returns and advantages of the recorded window (``slhip_training_batch_multi``), then the reference's

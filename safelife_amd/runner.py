@@ -1,5 +1,5 @@
 """
-``VectorRunner`` -- the driver loop of the reference's trainers, batched and device-resident.
+The driver loops of the reference's trainers, batched and device-resident.
 
 The reference steps a Python list of environments one by one: ``obs_for_envs`` collects the observations of
 the active agents, the algorithm's ``take_one_step`` runs the model on them and samples an action per agent
@@ -10,15 +10,22 @@ convolves (``policy_layout``), actions are sampled on the device, finished envs 
 kernel (``auto_reset``), and nothing visits the host.
 
 What carries over from the reference, per step and per agent (= per env for ``VectorRunner``, ``DQNRunner`` and
-``PipelinedRunner``; ``MultiAgentRunner`` and ``MultiAgentDQNRunner`` at the end of the file drive envs with several
-agents):
+``PipelinedRunner``; ``MultiAgentRunner`` and ``MultiAgentDQNRunner`` drive envs with several agents):
 ``obs, actions, rewards, done, next_obs, agent_ids, policies, values`` with the reference's meaning --
 ``done`` describes the step that was just taken, ``next_obs`` of a finished env is already the first
 observation of its next episode, and an agent id changes when its env resets (``(env index, resets so far)``
 instead of ``(id(env), env.num_resets, k)``), so trajectories are strung together exactly as
 ``gen_training_batch`` does.
+
+``VectorRunner``, ``DQNRunner``, ``MultiAgentRunner`` and ``MultiAgentDQNRunner`` are one loop, ``_Runner``: it reads
+the env's facts and holds every piece of a step that they share (first reset, model call, check of what the model
+returned, device draw, env step).  A runner puts the pieces in its order and adds what is its own: its draw, what its
+step result is made of, and ``gen_training_batch`` or ``collect``.  The two multi-agent runners keep who is active in an
+``_AgentState`` each.  ``PipelinedRunner`` is another loop (groups of envs on streams of their own).
 """
 import collections
+
+from . import _hip
 
 StepResult = collections.namedtuple("StepResult", "obs actions rewards done next_obs agent_ids policies values")
 DQNStep = collections.namedtuple("DQNStep", "obs actions rewards done next_obs agent_ids")
@@ -28,22 +35,119 @@ MultiAgentDQNStep = collections.namedtuple("MultiAgentDQNStep", DQNStep._fields 
 _SPLITMIX_G = 0x9E3779B97F4A7C15        # the increment of the draw kernel's splitmix64 (slhip_sample_actions)
 
 
-def _set_training_steps(env, num_steps):
-    """An env with a level schedule (schedule.LevelSchedule) evaluates its schedules at the runner's step count, as the
-    reference's LinearSchedule reads the logger's ``training_steps``."""
-    sched = getattr(env, "level_schedule", None)
-    if sched is not None:
-        sched.training_steps = int(num_steps)
+def _shifted_seed(seed, first_row):
+    """The seed for a draw kernel whose row 0 is row ``first_row`` of the whole run: a draw is then a function of
+    ``(seed, counter, row of the whole run)`` however the rows are dealt to shards or groups."""
+    return (int(seed) + _SPLITMIX_G * int(first_row)) & (2 ** 64 - 1)
 
 
-def _model_in(obs, cast_obs):
-    """What the model is handed: float32 (training/ppo.py:64, dqn.py:97), or with ``cast_obs=False`` the env's tensor as
-    it is (a uint8 policy tensor stays uint8)."""
-    import torch
-    return obs if (obs.dtype == torch.float32 or not cast_obs) else obs.to(torch.float32)
+def _float32_rows(torch, x):
+    """What the draw kernels read: float32, contiguous."""
+    return x if (x.dtype == torch.float32 and x.is_contiguous()) else x.to(torch.float32).contiguous()
 
 
-class VectorRunner(object):
+class _Runner(object):
+    """The loop under ``VectorRunner``, ``DQNRunner``, ``MultiAgentRunner`` and ``MultiAgentDQNRunner``: the checks of the
+    env, its facts (the single-agent env underneath, agents per env, rows = agents in all, the reward the trainers see)
+    and the pieces of a step.  A subclass says what only it knows in the class attributes below."""
+
+    _env_class, _multi_agent = "SafeLifeVectorEnv", False
+    _reloads = "finished envs reload inside the step kernel"
+    _bad_output = None                  # the ValueError of _draw_input
+
+    def __init__(self, env, cast_obs):
+        import torch
+        self.torch = torch
+        A = getattr(env, "n_agents", None)
+        if env.policy_tensor is None or (self._multi_agent and A is None):
+            raise ValueError("%s needs %s(policy_layout=...)" % (type(self).__name__, self._env_class))
+        self._base = getattr(env, "base", env)
+        if not self._base.auto_reset:
+            raise ValueError("%s needs auto_reset=True (%s)" % (type(self).__name__, self._reloads))
+        self.env, self.cast_obs = env, cast_obs
+        B = env.num_envs
+        self._per_agent = (B,) if A is None else (B, A)         # the shape of one entry per agent
+        self._rows = B * (1 if A is None else A)
+        self.env_ids = torch.arange(B, device=env.device, dtype=torch.int64)
+        self.num_steps = 0          # agent steps as ppo.py:134 / dqn.py:191 count them: env steps * envs
+        self._started = False
+
+    def _device_draws(self, seed):
+        """For a runner that draws with the library's kernels: the action of row ``r`` (agent ``a`` of env ``e`` is row
+        ``e * A + a``) at step ``c`` is a function of ``(seed, c, env_offset * A + r)`` and the model's output alone."""
+        self.seed = _shifted_seed(seed, self._base.env_offset * (self._rows // self.env.num_envs))
+        self.actions = self.torch.zeros(self._per_agent, dtype=self.torch.int32, device=self.env.device)
+        self.draws = 0              # the draw counter: steps taken
+        self._lib = _hip.lib()
+
+    def _reward(self):
+        """What the reference's trainers see is the reward as the wrapper stack hands it on (movement bonus, exit bonus,
+        side-effect penalty: env_factory.py:277-283 wraps the env before base_algo steps it): the wrapped reward when the
+        env was built with ``wrappers=``, the game's otherwise."""
+        shaped = getattr(self.env, "shaped_reward", None)
+        return shaped if shaped is not None else self.env.reward
+
+    def _obs(self):
+        """The env's observation tensor; the first call resets the envs (training/base_algo.py:166-171)."""
+        if not self._started:
+            self.env.reset()
+            self._started = True
+        return self.env.policy_tensor
+
+    def _agent_rows(self, obs):
+        """``obs`` with one row per agent."""
+        return obs
+
+    def _call(self, model, obs):
+        """The model on one row per agent: float32 (training/ppo.py:64, dqn.py:97), or with ``cast_obs=False`` the env's
+        tensor as it is (a uint8 policy tensor stays uint8)."""
+        torch = self.torch
+        x = self._agent_rows(obs)
+        with torch.no_grad():
+            return model(x if (x.dtype == torch.float32 or not self.cast_obs) else x.to(torch.float32))
+
+    def _draw_input(self, x):
+        """Probabilities or Q-values as the draw kernels read them: float32, contiguous, ``[rows, n]``."""
+        x = _float32_rows(self.torch, x)
+        if x.dim() != 2 or x.shape[0] != self._rows:
+            raise ValueError(self._bad_output)
+        return x
+
+    def _draw(self, entry, *args):
+        """One of the draw entry points into ``self.actions``, the int32 tensor the step kernel reads."""
+        rc = entry(*args, self.seed, self.draws, _hip.ptr(self.actions), _hip.current_stream_ptr())
+        if rc:
+            _hip.check(rc)
+        self.draws += 1
+
+    def _env_step(self, actions):
+        """The fused step -> own copies of ``rewards`` and ``done`` (bool).  An env with a level schedule
+        (schedule.LevelSchedule) evaluates its schedules at the runner's step count, as the reference's LinearSchedule
+        reads the logger's ``training_steps``."""
+        sched = getattr(self.env, "level_schedule", None)
+        if sched is not None:
+            sched.training_steps = int(self.num_steps)
+        self.env.step(actions)
+        return self._reward().clone(), self.env.done.to(self.torch.bool)
+
+
+class _ReplayCollector(object):
+    """``collect`` of the two DQN runners."""
+
+    def collect(self, steps, epsilon, replay):
+        """``steps`` steps of every env, each added to ``replay`` (``add_to_replay``: a ``ReplayBuffer``, or a
+        ``MultiAgentReplayBuffer`` for a multi-agent env); ``epsilon`` is a number or a function of ``num_steps`` (the
+        reference's ``epsilon_schedule``).  ``num_steps`` counts env steps * envs.  Returns the last step."""
+        step = None
+        for _ in range(int(steps)):
+            eps = epsilon(self.num_steps) if callable(epsilon) else epsilon
+            step = self.take_one_step(float(eps))
+            replay.add(step)
+            self.num_steps += self.env.num_envs
+        return step
+
+
+class VectorRunner(_Runner):
     """
     Parameters
     ----------
@@ -58,42 +162,25 @@ class VectorRunner(object):
     """
 
     def __init__(self, env, policy, generator=None, copy_obs=True, cast_obs=True):
-        import torch
-        self.torch = torch
-        if env.policy_tensor is None:
-            raise ValueError("VectorRunner needs SafeLifeVectorEnv(policy_layout=...)")
-        if not env.auto_reset:
-            raise ValueError("VectorRunner needs auto_reset=True (finished envs reload inside the step kernel)")
-        self.env, self.policy, self.generator, self.copy_obs, self.cast_obs = env, policy, generator, copy_obs, cast_obs
-        B = env.num_envs
-        self.env_ids = torch.arange(B, device=env.device, dtype=torch.int64)
-        self.num_resets = torch.zeros(B, device=env.device, dtype=torch.int64)       # env.num_resets of the reference
-        self.num_steps = 0
-        self._started = False
+        super(VectorRunner, self).__init__(env, cast_obs)
+        self.policy, self.generator, self.copy_obs = policy, generator, copy_obs
+        # env.num_resets of the reference
+        self.num_resets = self.torch.zeros(env.num_envs, device=env.device, dtype=self.torch.int64)
 
     def obs_for_envs(self):
         """Current observation of every env and its agent id ``(env index, resets so far)``; the first call
         resets the envs (training/base_algo.py:166-171)."""
-        if not self._started:
-            self.env.reset()
-            self._started = True
-        return self.env.policy_tensor, (self.env_ids, self.num_resets.clone())
+        return self._obs(), (self.env_ids, self.num_resets.clone())
 
     def act_on_envs(self, actions):
         """Step every env with its action; returns ``(next_obs, rewards, done)`` -- ``rewards`` is the wrapped
         (float64) reward when the env was built with ``wrappers=``, the game's float32 reward otherwise; the raw one
         stays available as ``env.reward``.  An env whose episode ended has
         already been reset: its ``next_obs`` row is the new episode's first observation and its reset counter is
-        bumped (training/base_algo.py:231-238)."""
+        bumped (training/base_algo.py:231-238).  ``num_steps`` counts the calls; ``gen_training_batch`` makes it the
+        reference's count."""
         torch = self.torch
-        a = actions.to(device=self.env.device, dtype=torch.int32).contiguous()
-        _set_training_steps(self.env, self.num_steps)
-        self.env.step(a)
-        # what the reference's trainers see is the reward as the wrapper stack hands it on (movement bonus, exit
-        # bonus, side-effect penalty: env_factory.py:277-283 wraps the env before base_algo steps it)
-        shaped = getattr(self.env, "shaped_reward", None)
-        rewards = shaped.clone() if shaped is not None else self.env.reward.clone()
-        done = self.env.done.to(torch.bool)
+        rewards, done = self._env_step(actions.to(device=self.env.device, dtype=torch.int32).contiguous())
         self.num_resets += done.to(torch.int64)
         self.num_steps += 1
         return self.env.policy_tensor, rewards, done
@@ -101,11 +188,9 @@ class VectorRunner(object):
     def take_one_step(self):
         """training/ppo.py:61-73 without the host: model forward, one categorical draw per env on the device,
         the fused step."""
-        torch = self.torch
         obs, agent_ids = self.obs_for_envs()
-        with torch.no_grad():
-            values, policies = self.policy(_model_in(obs, self.cast_obs))
-        actions = torch.multinomial(policies, 1, generator=self.generator).squeeze(1)
+        values, policies = self._call(self.policy, obs)
+        actions = self.torch.multinomial(policies, 1, generator=self.generator).squeeze(1)
         kept = obs.clone() if self.copy_obs else obs
         next_obs, rewards, done = self.act_on_envs(actions)
         return StepResult(kept, actions, rewards, done, next_obs, agent_ids, policies, values)
@@ -122,7 +207,6 @@ class VectorRunner(object):
         numpy arithmetic.  Returns the reference's ``obs actions action_prob returns advantages values``, flattened in
         time-major order (``rollout.py`` says how that differs from the reference's trajectory order); the buffer, with
         ``traj_start``, stays available as ``self.rollout`` and is overwritten by the next call."""
-        torch = self.torch
         from .rollout import RolloutBuffer
         T = int(steps_per_env)
         assert T > 0
@@ -141,15 +225,14 @@ class VectorRunner(object):
                 buf.record(t, step)
         finally:
             self.copy_obs = copy_obs
-        with torch.no_grad():
-            final_values = self.policy(_model_in(step.next_obs, self.cast_obs))[0]
+        final_values = self._call(self.policy, step.next_obs)[0]
         # training/ppo.py:134 counts agent steps: steps_per_env * len(training_envs)
         self.num_steps = steps_before + T * self.env.num_envs
         # (envs whose last step has `done` take 0.0 instead: the kernel looks at the flag itself)
         return buf.finish(final_values, gamma, lmda)
 
 
-class DQNRunner(object):
+class DQNRunner(_ReplayCollector, _Runner):
     """The driver loop of the reference's DQN (training/dqn.py:93-108, 177-191) without the host: Q-values from the
     model, the epsilon-greedy draw on the device (``slhip_sample_actions_eps``: ``argmax`` taking the first maximum, or a
     uniform action with probability epsilon, straight into the int32 tensor the step kernel reads), the fused step, and
@@ -161,66 +244,27 @@ class DQNRunner(object):
     False the env's tensor as it is.
     """
 
+    _bad_output = "q_model must return [num_envs, n_actions]"
+
     def __init__(self, env, q_model, seed=0, cast_obs=True):
-        import torch
-        from . import _hip
-        self.torch, self._hip = torch, _hip
-        if env.policy_tensor is None:
-            raise ValueError("DQNRunner needs SafeLifeVectorEnv(policy_layout=...)")
-        if not env.auto_reset:
-            raise ValueError("DQNRunner needs auto_reset=True (finished envs reload inside the step kernel)")
-        self.env, self.q_model, self.cast_obs = env, q_model, cast_obs
-        B = env.num_envs
-        self.seed = (int(seed) + _SPLITMIX_G * int(env.env_offset)) & (2 ** 64 - 1)
-        self.env_ids = torch.arange(B, device=env.device, dtype=torch.int64)
-        self.num_resets = torch.zeros(B, device=env.device, dtype=torch.int64)
-        self.actions = torch.zeros(B, dtype=torch.int32, device=env.device)
-        self.num_steps = 0          # agent steps, as dqn.py:191 counts them
-        self.draws = 0              # the draw counter: steps taken
-        self._started = False
-        self._lib = _hip.lib()
+        super(DQNRunner, self).__init__(env, cast_obs)
+        self.q_model = q_model
+        self._device_draws(seed)
+        self.num_resets = self.torch.zeros(env.num_envs, device=env.device, dtype=self.torch.int64)
 
     def take_one_step(self, epsilon):
         """``obs actions rewards done next_obs agent_ids`` of one step of every env: ``obs`` is an own copy (the step
         overwrites the env's tensor), ``actions`` an own int32 copy, ``rewards`` the wrapped float64 reward when the env
         has ``wrappers=``, the game's float32 reward otherwise; ``next_obs`` is the env's tensor -- valid until the next
         step, and for a finished env already the first observation of its next episode."""
-        torch, env, _hip = self.torch, self.env, self._hip
-        if not self._started:
-            env.reset()
-            self._started = True
-        obs = env.policy_tensor
+        obs = self._obs()
         agent_ids = (self.env_ids, self.num_resets.clone())
-        with torch.no_grad():
-            qvals = self.q_model(_model_in(obs, self.cast_obs))
-        if qvals.dtype != torch.float32 or not qvals.is_contiguous():
-            qvals = qvals.to(torch.float32).contiguous()
-        if qvals.dim() != 2 or qvals.shape[0] != env.num_envs:
-            raise ValueError("q_model must return [num_envs, n_actions]")
-        rc = self._lib.slhip_sample_actions_eps(_hip.ptr(qvals), env.num_envs, qvals.shape[1], float(epsilon), self.seed,
-                                                self.draws, _hip.ptr(self.actions), _hip.current_stream_ptr())
-        if rc:
-            _hip.check(rc)
-        self.draws += 1
+        qvals = self._draw_input(self._call(self.q_model, obs))
+        self._draw(self._lib.slhip_sample_actions_eps, _hip.ptr(qvals), self._rows, qvals.shape[1], float(epsilon))
         kept = obs.clone()
-        _set_training_steps(env, self.num_steps)
-        env.step(self.actions)
-        shaped = getattr(env, "shaped_reward", None)
-        rewards = shaped.clone() if shaped is not None else env.reward.clone()
-        done = env.done.to(torch.bool)
-        self.num_resets += done.to(torch.int64)
-        return DQNStep(kept, self.actions.clone(), rewards, done, env.policy_tensor, agent_ids)
-
-    def collect(self, steps, epsilon, replay):
-        """``steps`` steps of every env, each added to ``replay`` (``add_to_replay``); ``epsilon`` is a number or a
-        function of ``num_steps`` (the reference's ``epsilon_schedule``).  Returns the last step."""
-        step = None
-        for _ in range(int(steps)):
-            eps = epsilon(self.num_steps) if callable(epsilon) else epsilon
-            step = self.take_one_step(float(eps))
-            replay.add(step)
-            self.num_steps += self.env.num_envs
-        return step
+        rewards, done = self._env_step(self.actions)
+        self.num_resets += done.to(self.torch.int64)
+        return DQNStep(kept, self.actions.clone(), rewards, done, self.env.policy_tensor, agent_ids)
 
 
 class PipelinedRunner(object):
@@ -247,7 +291,6 @@ class PipelinedRunner(object):
 
     def __init__(self, env, policy, seed=0, on_step=None, sampler="device", generator=None):
         import torch
-        from . import _hip
         self.torch, self._hip = torch, _hip
         if env.policy_tensor is None or not env.auto_reset or env.slices < 2:
             raise ValueError("PipelinedRunner needs SafeLifeVectorEnv(policy_layout=..., auto_reset=True, slices>=2)")
@@ -267,8 +310,7 @@ class PipelinedRunner(object):
             st = env.slice_stream(g)
             # (the kernel's env e of this group is env offset + lo + e of the whole run: see slhip_sample_actions)
             self._groups.append((g, lo, hi, st, torch.cuda.stream(st), env.policy_tensor[lo:hi],
-                                 self.actions.data_ptr() + 4 * lo, st.cuda_stream,
-                                 (self.seed + _SPLITMIX_G * (offset + lo)) & (2 ** 64 - 1)))
+                                 self.actions.data_ptr() + 4 * lo, st.cuda_stream, _shifted_seed(self.seed, offset + lo)))
 
     def start(self):
         if not self._started:
@@ -294,8 +336,7 @@ class PipelinedRunner(object):
             with torch.no_grad():
                 values, probs = self.policy(obs)
             if self.sampler == "device":
-                if probs.dtype != torch.float32 or not probs.is_contiguous():
-                    probs = probs.to(torch.float32).contiguous()
+                probs = _float32_rows(torch, probs)
                 rc = self._lib.slhip_sample_actions(probs.data_ptr(), hi - lo, probs.shape[1], group_seed, draw, act_ptr,
                                                     st_ptr)
                 if rc:
@@ -320,108 +361,110 @@ class PipelinedRunner(object):
         self.env.join()
 
 
-class MultiAgentRunner(object):
-    """The driver loop of the reference's trainers for envs with SEVERAL agents (training/base_algo.py:152-244 with
-    training/ppo.py:61-143), without the host.  The agents of one env finish at different steps; a finished agent gets no
-    action (the env is handed 0 for it) and no row in the training batch until its env reloads, which happens -- inside the
-    step kernel -- once ALL its agents are done.  Who is active is kept on the device (``active`` uint8 ``[B, A]``, the
-    reference's ``~last_done``; ``num_resets`` int64 ``[B]``) and carried from step to step and from one
-    ``gen_training_batch`` to the next.
+class _AgentState(object):
+    """What a multi-agent run carries from step to step, owned by its runner for the runner's whole life: ``active``
+    uint8 ``[B, A]`` (who takes part in the NEXT step; the reference's ``~last_done``) and ``num_resets`` int64 ``[B]``.
+    They are ``active_now`` / ``num_resets`` of ``buffer``, a one-step ``MultiAgentRolloutBuffer``: one kernel holds the
+    rule that moves them on (``k_rollout_record_multi``), one launch per step, whether the step goes into a window
+    (``window.record(t, step, state.buffer)``) or into no window at all (``advance``)."""
 
-    The reference hands its model the active agents' observations only.  Here the policy is called on ALL ``B * A`` rows
-    and what it returns for inactive rows is ignored (their action is 0 whatever the probabilities hold, NaN included):
-    a compacted input would need the active count on the host every step.  The action of agent ``a`` of env ``e`` at step
-    ``c`` is the draw of ``slhip_sample_actions`` for row ``(env_offset + e) * A + a`` under ``(seed, c)``.
+    _Step = collections.namedtuple("_Step", "obs actions rewards done policies values")
 
-    Parameters: ``env`` a ``SafeLifeMultiAgentVectorEnv(policy_layout=..., auto_reset=True)``;
-    ``policy(obs [B*A, C, vw, vh]) -> (values [B*A], probs float32 [B*A, n_actions])`` on the device; ``cast_obs``: True
-    hands the model float32 (training/ppo.py:64), False the env's tensor as it is.
-    """
-
-    def __init__(self, env, policy, seed=0, cast_obs=True):
-        import torch
-        from . import _hip
+    def __init__(self, num_envs, n_agents, reward_dtype, device):
         from .rollout import MultiAgentRolloutBuffer
-        self.torch, self._hip, self._buffer = torch, _hip, MultiAgentRolloutBuffer
-        if getattr(env, "n_agents", None) is None or env.policy_tensor is None:
-            raise ValueError("MultiAgentRunner needs SafeLifeMultiAgentVectorEnv(policy_layout=...)")
-        if not env.base.auto_reset:
-            raise ValueError("MultiAgentRunner needs auto_reset=True (an env reloads inside the step kernel once all its "
-                             "agents are done)")
-        self.env, self.policy, self.cast_obs = env, policy, cast_obs
-        B, A = env.num_envs, env.n_agents
-        self.seed = (int(seed) + _SPLITMIX_G * int(env.base.env_offset) * A) & (2 ** 64 - 1)
-        self.env_ids = torch.arange(B, device=env.device, dtype=torch.int64)
-        self.actions = torch.zeros((B, A), dtype=torch.int32, device=env.device)
-        #: agent steps taken so far -- what ppo.py:134 would count with per-agent lists -- as a device tensor
-        self.num_agent_steps = torch.zeros(1, dtype=torch.int64, device=env.device)
-        self.num_steps = 0          # env steps * envs, as ppo.py:134 counts
-        self.draws = 0              # the draw counter: steps taken
-        self.rollout = None
-        # the carried state lives in a one-step buffer until gen_training_batch makes the real one
-        self._state = MultiAgentRolloutBuffer(B, A, 1, None, None, self._reward_dtype(), env.device)
-        self._started = False
-        self._lib = _hip.lib()
+        self.buffer = buf = MultiAgentRolloutBuffer(num_envs, n_agents, 1, None, None, reward_dtype, device)
+        self.active, self.num_resets = buf.active_now, buf.num_resets
+        self._zeros = buf.torch.zeros(num_envs * n_agents, dtype=buf.torch.float32, device=buf.device)
 
-    def _reward_dtype(self):
-        env = self.env
-        return (env.shaped_reward if env.shaped_reward is not None else env.reward).dtype
+    def advance(self, step, policies=None):
+        """Past ``step`` (its actions, rewards and done) outside a window: the row goes into the buffer's own one step,
+        which nobody reads.  A step without policies and values, a DQN step, hands in what stands for its probabilities
+        -- its Q-values ``[B * A, n]`` -- and zeros stand for its values."""
+        if policies is not None:
+            step = self._Step(None, step.actions, step.rewards, step.done, policies, self._zeros)
+        self.buffer.record(0, step)
+
+
+class _MultiAgentRunner(_Runner):
+    """The two multi-agent runners: the agents of one env finish at different steps; a finished agent gets no action (the
+    env is handed 0 for it) until its env reloads, which happens -- inside the step kernel -- once ALL its agents are done.
+    Who is active is kept on the device, in an ``_AgentState``.  The model is called on ALL ``B * A`` rows and what it
+    returns for inactive rows is ignored (their action is 0 whatever it holds, NaN included): a compacted input would need
+    the active count on the host every step."""
+
+    _env_class, _multi_agent = "SafeLifeMultiAgentVectorEnv", True
+    _reloads = "an env reloads inside the step kernel once all its agents are done"
+
+    def __init__(self, env, seed, cast_obs):
+        super(_MultiAgentRunner, self).__init__(env, cast_obs)
+        self._device_draws(seed)
+        #: active agent steps taken so far -- what ppo.py:134 would count with per-agent lists -- as a device tensor
+        self.num_agent_steps = self.torch.zeros(1, dtype=self.torch.int64, device=env.device)
+        self._state = _AgentState(env.num_envs, env.n_agents, self._reward().dtype, env.device)
 
     @property
     def active(self):
         """uint8 [B, A]: who takes part in the NEXT step."""
-        return self._state.active_now
+        return self._state.active
 
     @property
     def num_resets(self):
         """int64 [B]: reloads of every env so far (``env.num_resets`` of the reference)."""
         return self._state.num_resets
 
-    def _model_in(self, obs):
-        return _model_in(obs.view((-1,) + tuple(obs.shape[2:])), self.cast_obs)
+    def _agent_rows(self, obs):
+        return obs.view((self._rows,) + tuple(obs.shape[2:]))
+
+    def _masked_step(self, obs, x, entry, *epsilon):
+        """From the model's checked output ``x`` on: the masked draw, the fused step, the agent-step count -- everything
+        but moving the state on.  -> ``obs actions rewards done next_obs agent_ids active``, the first two own copies."""
+        active = self._state.active.clone()
+        agent_ids = (self.env_ids, self._state.num_resets.clone())
+        self._draw(entry, _hip.ptr(x), _hip.ptr(active), self._rows, x.shape[1], *epsilon)
+        kept = obs.clone()
+        rewards, done = self._env_step(self.actions)
+        self.num_agent_steps += active.sum()
+        return kept, self.actions.clone(), rewards, done, self.env.policy_tensor, agent_ids, active
+
+
+class MultiAgentRunner(_MultiAgentRunner):
+    """The driver loop of the reference's trainers for envs with SEVERAL agents (training/base_algo.py:152-244 with
+    training/ppo.py:61-143), without the host.  A finished agent gets no row in the training batch until its env
+    reloads.  ``active`` and ``num_resets`` are carried from step to step and from one ``gen_training_batch`` to the next,
+    whatever the windows' lengths and whatever single steps lie between them.
+
+    The action of agent ``a`` of env ``e`` at step ``c`` is the draw of ``slhip_sample_actions`` for row
+    ``(env_offset + e) * A + a`` under ``(seed, c)``.
+
+    Parameters: ``env`` a ``SafeLifeMultiAgentVectorEnv(policy_layout=..., auto_reset=True)``;
+    ``policy(obs [B*A, C, vw, vh]) -> (values [B*A], probs float32 [B*A, n_actions])`` on the device; ``cast_obs``: True
+    hands the model float32 (training/ppo.py:64), False the env's tensor as it is.
+    """
+
+    _bad_output = "policy must return probabilities [num_envs * n_agents, n_actions]"
+
+    def __init__(self, env, policy, seed=0, cast_obs=True):
+        super(MultiAgentRunner, self).__init__(env, seed, cast_obs)
+        self.policy = policy
+        self.rollout = None
 
     def _step(self):
-        """Model, masked draw, fused step -- everything but the bookkeeping, which ``record_multi`` does."""
-        torch, env, _hip = self.torch, self.env, self._hip
-        if not self._started:
-            env.reset()
-            self._started = True
-        B, A = env.num_envs, env.n_agents
-        obs = env.policy_tensor
-        with torch.no_grad():
-            values, policies = self.policy(self._model_in(obs))
-        if policies.dtype != torch.float32 or not policies.is_contiguous():
-            policies = policies.to(torch.float32).contiguous()
-        if policies.dim() != 2 or policies.shape[0] != B * A:
-            raise ValueError("policy must return probabilities [num_envs * n_agents, n_actions]")
-        state = self._state
-        active = state.active_now.clone()
-        agent_ids = (self.env_ids, state.num_resets.clone())
-        rc = self._lib.slhip_sample_actions_masked(_hip.ptr(policies), _hip.ptr(active), B * A, policies.shape[1],
-                                                   self.seed, self.draws, _hip.ptr(self.actions),
-                                                   _hip.current_stream_ptr())
-        if rc:
-            _hip.check(rc)
-        self.draws += 1
-        kept = obs.clone()
-        _set_training_steps(env, self.num_steps)
-        env.step(self.actions)
-        rewards = (env.shaped_reward if env.shaped_reward is not None else env.reward).clone()
-        done = env.done.to(torch.bool)
-        self.num_agent_steps += active.sum()
-        self.num_steps += B
-        return MultiAgentStep(kept, self.actions.clone(), rewards, done, env.policy_tensor, agent_ids,
-                              policies.view(B, A, -1), values.reshape(B, A), active)
+        """Model, masked draw, fused step; the caller moves the state on."""
+        obs = self._obs()
+        values, policies = self._call(self.policy, obs)
+        policies = self._draw_input(policies)
+        step = self._masked_step(obs, policies, self._lib.slhip_sample_actions_masked)
+        self.num_steps += self.env.num_envs
+        return MultiAgentStep(*step[:6], policies.view(self._per_agent + (-1,)), values.reshape(self._per_agent), step[6])
 
     def take_one_step(self):
         """One step of every env: the ``StepResult`` fields shaped ``[B, A, ...]`` plus ``active`` uint8 ``[B, A]`` -- who
         took part; the rows of the others are to be ignored (their action is 0).  ``agent_ids`` is ``(env index [B],
         resets so far [B])``, the agent being the column.  ``rewards`` is ``env.shaped_reward`` when the env has
-        ``wrappers=``, else ``env.reward``; ``next_obs`` is the env's tensor, valid until the next step.  (The bookkeeping
-        runs through row 0 of the buffer that holds the carried state -- after a ``gen_training_batch`` that is
-        ``self.rollout``, whose window is then no longer whole.)"""
+        ``wrappers=``, else ``env.reward``; ``next_obs`` is the env's tensor, valid until the next step.  The step is
+        recorded nowhere: ``self.rollout`` and the batch of the last ``gen_training_batch`` stay as they are."""
         step = self._step()
-        self._state.record(0, step)         # moves active / num_resets on (the one-step window itself is not used)
+        self._state.advance(step)
         return step
 
     def gen_training_batch(self, steps_per_env, gamma=0.97, lmda=0.95, gather_obs=True, dense=False):
@@ -431,82 +474,43 @@ class MultiAgentRunner(object):
         advantages, and the active rows gathered in ``(t, b, a)`` order -- bit exact with the reference's numpy
         arithmetic.  One host visit per window (the row count; none with ``dense=True``).  ``active`` and ``num_resets``
         persist: the next window starts with whoever is gone now."""
-        torch, env = self.torch, self.env
+        from .rollout import MultiAgentRolloutBuffer
+        env = self.env
         T = int(steps_per_env)
         assert T > 0
         step = self._step()
         buf = self.rollout
         if (buf is None or buf.steps != T or buf.reward_dtype != step.rewards.dtype
                 or buf.obs.shape[2:] != step.obs.shape[2:] or buf.obs.dtype != step.obs.dtype):
-            buf = self.rollout = self._buffer(env.num_envs, env.n_agents, T, tuple(step.obs.shape[2:]), step.obs.dtype,
-                                              step.rewards.dtype, env.device)
-        if buf is not self._state:           # the carried state moves into the window's buffer
-            buf.active_now.copy_(self._state.active_now)
-            buf.num_resets.copy_(self._state.num_resets)
-            self._state = buf
-        buf.record(0, step)
+            buf = self.rollout = MultiAgentRolloutBuffer(env.num_envs, env.n_agents, T, tuple(step.obs.shape[2:]),
+                                                         step.obs.dtype, step.rewards.dtype, env.device)
+        buf.record(0, step, self._state.buffer)
         for t in range(1, T):
             step = self._step()
-            buf.record(t, step)
-        with torch.no_grad():
-            final_values = self.policy(self._model_in(step.next_obs))[0]
-        return buf.finish(final_values.reshape(env.num_envs, env.n_agents), gamma, lmda, gather_obs=gather_obs, dense=dense)
+            buf.record(t, step, self._state.buffer)
+        final_values = self._call(self.policy, step.next_obs)[0]
+        return buf.finish(final_values.reshape(self._per_agent), gamma, lmda, gather_obs=gather_obs, dense=dense)
 
 
-class MultiAgentDQNRunner(object):
+class MultiAgentDQNRunner(_ReplayCollector, _MultiAgentRunner):
     """``DQNRunner`` for envs with SEVERAL agents: the reference's DQN (training/dqn.py:93-108, 177-191) over
-    ``obs_for_envs`` / ``act_on_envs`` (training/base_algo.py:152-244), without the host.  A finished agent gets no action
-    (the env is handed 0 for it) and no row in the replay buffer until its env reloads, which happens -- inside the step
-    kernel -- once ALL its agents are done.  Who is active (``active`` uint8 ``[B, A]``, ``num_resets`` int64 ``[B]``) is
-    kept on the device and moved on once per step by ``slhip_rollout_record_multi``, through a one-step
-    ``MultiAgentRolloutBuffer`` as in ``MultiAgentRunner``: there is one implementation of that rule.
+    ``obs_for_envs`` / ``act_on_envs`` (training/base_algo.py:152-244), without the host.  A finished agent gets no row in
+    the replay buffer until its env reloads.  ``collect`` counts env steps * envs in ``num_steps`` and the active agent
+    steps in ``num_agent_steps``.
 
-    ``q_model`` is called on ALL ``B * A`` rows and what it returns for inactive rows is ignored (NaN included): a
-    compacted input would need the active count on the host every step.  The action of agent ``a`` of env ``e`` at step
-    ``c`` is the draw of ``slhip_sample_actions_eps`` for row ``(env_offset + e) * A + a`` under ``(seed, c)``.
+    The action of agent ``a`` of env ``e`` at step ``c`` is the draw of ``slhip_sample_actions_eps`` for row
+    ``(env_offset + e) * A + a`` under ``(seed, c)``.
 
     Parameters: ``env`` a ``SafeLifeMultiAgentVectorEnv(policy_layout=..., auto_reset=True)``;
     ``q_model(obs [B*A, C, vw, vh]) -> qvals [B*A, n_actions]`` on the device; ``cast_obs``: True hands the model float32
     (dqn.py:97), False the env's tensor as it is.
     """
 
-    _StateStep = collections.namedtuple("_StateStep", "obs actions rewards done policies values")
+    _bad_output = "q_model must return [num_envs * n_agents, n_actions]"
 
     def __init__(self, env, q_model, seed=0, cast_obs=True):
-        import torch
-        from . import _hip
-        from .rollout import MultiAgentRolloutBuffer
-        self.torch, self._hip = torch, _hip
-        if getattr(env, "n_agents", None) is None or env.policy_tensor is None:
-            raise ValueError("MultiAgentDQNRunner needs SafeLifeMultiAgentVectorEnv(policy_layout=...)")
-        if not env.base.auto_reset:
-            raise ValueError("MultiAgentDQNRunner needs auto_reset=True (an env reloads inside the step kernel once all "
-                             "its agents are done)")
-        self.env, self.q_model, self.cast_obs = env, q_model, cast_obs
-        B, A = env.num_envs, env.n_agents
-        self.seed = (int(seed) + _SPLITMIX_G * int(env.base.env_offset) * A) & (2 ** 64 - 1)
-        self.env_ids = torch.arange(B, device=env.device, dtype=torch.int64)
-        self.actions = torch.zeros((B, A), dtype=torch.int32, device=env.device)
-        #: active agent steps taken so far, as a device tensor
-        self.num_agent_steps = torch.zeros(1, dtype=torch.int64, device=env.device)
-        self.num_steps = 0          # env steps * envs, as dqn.py:191 counts
-        self.draws = 0              # the draw counter: steps taken
-        reward = env.shaped_reward if env.shaped_reward is not None else env.reward
-        # the carried state and the one kernel that moves it on (the one-step window itself is not used)
-        self._state = MultiAgentRolloutBuffer(B, A, 1, None, None, reward.dtype, env.device)
-        self._no_values = torch.zeros(B * A, dtype=torch.float32, device=env.device)
-        self._started = False
-        self._lib = _hip.lib()
-
-    @property
-    def active(self):
-        """uint8 [B, A]: who takes part in the NEXT step."""
-        return self._state.active_now
-
-    @property
-    def num_resets(self):
-        """int64 [B]: reloads of every env so far (``env.num_resets`` of the reference)."""
-        return self._state.num_resets
+        super(MultiAgentDQNRunner, self).__init__(env, seed, cast_obs)
+        self.q_model = q_model
 
     def take_one_step(self, epsilon):
         """``obs actions rewards done next_obs agent_ids active`` of one step of every env, the fields shaped
@@ -515,46 +519,8 @@ class MultiAgentDQNRunner(object):
         copy, ``rewards`` is ``env.shaped_reward`` when the env has ``wrappers=``, else ``env.reward``; ``next_obs`` is the
         env's tensor, valid until the next step; ``agent_ids`` is ``(env index [B], resets so far [B])``, the agent being
         the column."""
-        torch, env, _hip = self.torch, self.env, self._hip
-        if not self._started:
-            env.reset()
-            self._started = True
-        B, A = env.num_envs, env.n_agents
-        obs = env.policy_tensor
-        with torch.no_grad():
-            qvals = self.q_model(_model_in(obs.view((-1,) + tuple(obs.shape[2:])), self.cast_obs))
-        if qvals.dtype != torch.float32 or not qvals.is_contiguous():
-            qvals = qvals.to(torch.float32).contiguous()
-        if qvals.dim() != 2 or qvals.shape[0] != B * A:
-            raise ValueError("q_model must return [num_envs * n_agents, n_actions]")
-        state = self._state
-        active = state.active_now.clone()
-        agent_ids = (self.env_ids, state.num_resets.clone())
-        rc = self._lib.slhip_sample_actions_eps_masked(_hip.ptr(qvals), _hip.ptr(active), B * A, qvals.shape[1],
-                                                       float(epsilon), self.seed, self.draws, _hip.ptr(self.actions),
-                                                       _hip.current_stream_ptr())
-        if rc:
-            _hip.check(rc)
-        self.draws += 1
-        kept = obs.clone()
-        _set_training_steps(env, self.num_steps)
-        env.step(self.actions)
-        rewards = (env.shaped_reward if env.shaped_reward is not None else env.reward).clone()
-        done = env.done.to(torch.bool)
-        self.num_agent_steps += active.sum()
-        step = MultiAgentDQNStep(kept, self.actions.clone(), rewards, done, env.policy_tensor, agent_ids, active)
-        # active / num_resets move on (the Q-values stand in for the probabilities of the window nobody reads)
-        state.record(0, self._StateStep(None, step.actions, rewards, done, qvals, self._no_values))
-        return step
-
-    def collect(self, steps, epsilon, replay):
-        """``steps`` steps of every env, each added to ``replay`` (a ``MultiAgentReplayBuffer``); ``epsilon`` is a number
-        or a function of ``num_steps`` (the reference's ``epsilon_schedule``).  ``num_steps`` counts env steps * envs,
-        ``num_agent_steps`` the active agent steps.  Returns the last step."""
-        step = None
-        for _ in range(int(steps)):
-            eps = epsilon(self.num_steps) if callable(epsilon) else epsilon
-            step = self.take_one_step(float(eps))
-            replay.add(step)
-            self.num_steps += self.env.num_envs
+        obs = self._obs()
+        qvals = self._draw_input(self._call(self.q_model, obs))
+        step = MultiAgentDQNStep(*self._masked_step(obs, qvals, self._lib.slhip_sample_actions_eps_masked, float(epsilon)))
+        self._state.advance(step, qvals)
         return step

@@ -502,3 +502,142 @@ def test_gen_training_batch_multi_end_to_end(wrapped):
         reloads += int(D.astype(bool).all(axis=2).sum())
     # the run held what it is here for: agents away while their env went on, and envs reloading inside a window
     assert gaps > 0 and reloads > 0
+
+
+# ------------------------------------------------------------------------- the carried state, windows and single steps
+
+def _pair():
+    """Two identical envs (game reward) on the spec levels with two agents, and the exact policy for them."""
+    import torch
+    from safelife_amd.levels import LevelPool
+    levels = spec_levels()
+    pool = LevelPool(levels, counts_fn=_device_counts, n_agents=2, min_performance_fraction=E2E["min_performance_fraction"])
+    a, b = _env(pool, len(levels), False), _env(pool, len(levels), False)
+    return a, b, ExactPolicy(torch, tuple(a.policy_tensor.shape[2:]), a.device)
+
+
+def _log_actions(env):
+    """-> the list that collects a clone of every action tensor ``env.step`` is handed from now on."""
+    handed, env_step = [], env.step
+
+    def logging_step(actions):
+        handed.append(actions.clone())
+        return env_step(actions)
+
+    env.step = logging_step
+    return handed
+
+
+def _by_hand(env, policy, acts):
+    """Step ``env`` with the actions ``acts`` [T,B,A]: -> numpy R, D, V [T,B,A] and V(next_obs) [B,A] of the last step."""
+    import torch
+    B, A = acts.shape[1:]
+    rows = lambda o: o.view((B * A,) + tuple(o.shape[2:]))
+    R, D, V = [], [], []
+    for t in range(acts.shape[0]):
+        V.append(policy(rows(env.policy_tensor))[0].view(B, A))
+        env.step(acts[t])
+        R.append(env.reward.clone()), D.append(env.done.clone())
+    fv = policy(rows(env.policy_tensor))[0].view(B, A)
+    return tuple(torch.stack(x).cpu().numpy() for x in (R, D, V)) + (fv.cpu().numpy(),)
+
+
+def test_windows_and_single_steps_interleaved():
+    """gen_training_batch(6), three take_one_step(), gen_training_batch(4) -- another length, so another window buffer --
+    against gae_multi_ref fed with the step stream of a second env stepped by hand with the recorded actions, the state
+    carried across the single steps by the reference's rule (gae_multi_ref.bookkeeping): both windows' rows and agent
+    ids, returns and advantages bit for bit, and active / num_resets / num_agent_steps / num_steps after every phase."""
+    import torch
+    from safelife_amd.runner import MultiAgentRunner
+    B, A = E2E["B"], 2
+    a, b, policy = _pair()
+    runner = MultiAgentRunner(a, policy, seed=E2E["seed"])
+    handed = _log_actions(a)
+    b.reset()
+    now = dict(active=np.ones((B, A), bool), resets=np.zeros(B, np.int64), agent_steps=0, env_steps=0, gaps=0)
+
+    def state_is_carried(where):
+        assert np.array_equal(runner.active.cpu().numpy() != 0, now["active"]), where
+        assert np.array_equal(runner.num_resets.cpu().numpy(), now["resets"]), where
+        assert int(runner.num_agent_steps.item()) == now["agent_steps"], where
+        assert runner.num_steps == now["env_steps"] * B, where
+
+    def window(T):
+        del handed[:]
+        batch = runner.gen_training_batch(T, gamma=0.97, lmda=0.95)
+        buf = runner.rollout
+        buf.check_status()
+        R, D, V, fv = _by_hand(b, policy, torch.stack(handed))
+        ref = gae_multi_ref.window(R, D, V, fv, 0.97, 0.95, now["active"], now["resets"])
+        assert buf.steps == T and np.array_equal(buf.rows.cpu().numpy(), ref.rows), T
+        assert np.array_equal(buf.agent_ids.cpu().numpy(), ref.agent_ids), T
+        assert np.array_equal(bits(batch.returns.cpu().numpy()), bits(ref.returns.reshape(-1)[ref.rows])), T
+        assert np.array_equal(bits(batch.advantages.cpu().numpy()), bits(ref.advantages.reshape(-1)[ref.rows])), T
+        now.update(active=ref.active_end, resets=ref.resets_end, agent_steps=now["agent_steps"] + len(ref.rows),
+                   env_steps=now["env_steps"] + T, gaps=now["gaps"] + int((ref.active == 0).sum()))
+        state_is_carried("window of %d" % T)
+        return buf
+
+    first = window(6)
+    reloads = 0
+    for k in range(3):
+        del handed[:]
+        step = runner.take_one_step()
+        R, D, V, fv = _by_hand(b, policy, torch.stack(handed))
+        assert np.array_equal(step.active.cpu().numpy() != 0, now["active"]), k
+        assert np.array_equal(step.agent_ids[1].cpu().numpy(), now["resets"]), k
+        assert np.array_equal(step.done.cpu().numpy(), D[0].astype(bool)), k
+        took_part, _, active, resets = gae_multi_ref.bookkeeping(D, now["active"], now["resets"])
+        reloads += int((resets != now["resets"]).sum())
+        now.update(active=active, resets=resets, agent_steps=now["agent_steps"] + int(took_part.sum()),
+                   env_steps=now["env_steps"] + 1, gaps=now["gaps"] + int((~took_part).sum()))
+        state_is_carried("single step %d" % k)
+    assert window(4) is not first
+    # the run held what it is here for: an agent away while its env went on, and an env reloading between the windows
+    print("gaps %d, reloads during the single steps %d" % (now["gaps"], reloads))
+    assert now["gaps"] > 0 and reloads > 0
+
+
+def test_a_finished_window_stays_whole():
+    """The dense batch of a window hands out the window buffer's own tensors: single steps taken afterwards leave them,
+    and the window's ``active``, as they were."""
+    import torch
+    from safelife_amd.runner import MultiAgentRunner
+    a, _, policy = _pair()
+    runner = MultiAgentRunner(a, policy, seed=E2E["seed"])
+    dense = runner.gen_training_batch(6, dense=True)
+    live = dict(dense._asdict(), window_active=runner.rollout.active)
+    kept = {name: x.clone() for name, x in live.items()}
+    for _ in range(2):
+        runner.take_one_step()
+    torch.cuda.synchronize()
+    for name in live:
+        assert torch.equal(live[name], kept[name]), name
+
+
+def test_the_dqn_runner_moves_the_same_state():
+    """MultiAgentRunner under a policy that puts probability 1 on the argmax of the Q-model's values, and
+    MultiAgentDQNRunner with epsilon 0, on two identical envs: the same ``active`` and ``num_resets`` and the same ``done``
+    after every one of 12 steps (time limit 9: every env reloads on the way)."""
+    import torch
+    from safelife_amd.runner import MultiAgentDQNRunner, MultiAgentRunner
+    a, b, exact = _pair()
+
+    def q_model(obs):
+        return exact(obs)[1]                    # (one entry of 3/4 among entries of 1/32: the argmax is unique)
+
+    def policy(obs):
+        q = q_model(obs)
+        probs = torch.zeros_like(q)
+        probs[torch.arange(q.shape[0], device=q.device), q.argmax(dim=1)] = 1.0
+        return q[:, 0], probs
+
+    ppo, dqn = MultiAgentRunner(a, policy, seed=5), MultiAgentDQNRunner(b, q_model, seed=11)
+    away = 0
+    for t in range(12):
+        s, d = ppo.take_one_step(), dqn.take_one_step(0.0)
+        assert torch.equal(s.active, d.active) and torch.equal(s.done, d.done) and torch.equal(a.done, b.done), t
+        assert torch.equal(ppo.active, dqn.active) and torch.equal(ppo.num_resets, dqn.num_resets), t
+        away += int((ppo.active == 0).sum().item())
+    print("agents away %d, reloads %d" % (away, int(ppo.num_resets.sum().item())))
+    assert away > 0 and int(ppo.num_resets.min().item()) >= 1
