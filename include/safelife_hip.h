@@ -1068,6 +1068,115 @@ int slhip_schedule_required_multi(const sl_level_schedule_multi *m, double fract
  * Needs of *m: s (groups, rings, cur_slot), n_agents, reward_possible, out. */
 int slhip_schedule_harvest_multi(const sl_level_schedule_multi *m, const sl_env_scalars *scalars, int B, void *stream);
 
+/* ---- the episode log: rows, combined score, running summaries (additive to ABI 13: four new symbols and one new struct,
+ * nothing existing changes, so SL_ABI_VERSION stays where it is) ---------------------------------------------------------
+ * The arithmetic of the reference's SafeLifeLogger (safelife_logger.py): log_episode() :262-354 with combined_score()
+ * :671-716 per finished episode, the running summaries of log_scalars() :372-381, and summarize_run_file() :719-762 over the
+ * rows.  Files, tensorboard, wandb and video stay with the host.  Single-agent batches only.
+ *
+ * A finished episode becomes a ROW.  Row i (counted from the log's start) lives at rows[i % capacity]; a row is valid while
+ * i >= n_rows - capacity and rows[i % capacity].index == i.  All float64 arithmetic is unfused, every operation rounded on
+ * its own. */
+typedef struct sl_episode_log_row { /* 96 bytes */
+    int64_t index;                /* the row's own global index */
+    int64_t training_steps;       /* the reference's cumulative <type>_steps when log_episode() ran for this episode */
+    int64_t prev;                 /* global index of the same env's previous row, -1: none */
+    int32_t env;
+    int32_t level;                /* the pool slot the episode was played on */
+    int32_t episode_idx;          /* the env's episode counter during that episode (sl_episode_record.episode_idx) */
+    int32_t length;               /* info['episode']['length'] */
+    float reward;                 /* info['episode']['reward'] */
+    int32_t reward_possible;      /* initial_available_points() + points_on_level_exit of that slot */
+    int32_t reward_needed;        /* required_points() of the episode */
+    uint8_t success, times_up;
+    uint8_t flags;                /* SL_LOG_JOINED: slhip_episode_log_join has filled the four side-effect fields */
+    uint8_t reserved;
+    double reward_frac;           /* f64(reward) / f64(max(reward_possible, 1)) */
+    double side_effects[2];       /* the weighted totals (agent, inaction); NaN until joined */
+    double side_effects_frac;     /* side_effects[0] / np.maximum(side_effects[1], 1); NaN until joined */
+    double score;                 /* combined_score(); NaN until joined */
+} sl_episode_log_row;
+#define SL_LOG_JOINED 1
+#define SL_LOG_KEYS 5             /* summaries, in the reference's order: side_effects, length, reward, success, score */
+#define SL_LOG_COUNTERS 5         /* counters[]: n_rows, steps, episodes, summarised, unmatched */
+#define SL_LOG_MAX_HOPS 64        /* rows slhip_episode_log_join follows along `prev` before it gives an entry up */
+#define SL_LOG_RUN_SUMMARY 12     /* doubles slhip_episode_log_run_summary writes */
+
+typedef struct sl_episode_log {   /* 104 bytes; every pointer is device memory */
+    int64_t capacity;             /* rows of the ring, >= B (one harvest never laps itself) */
+    int32_t B, L;                 /* envs; pool slots */
+    double polyak;                /* summary_polyak: 0.99 for training, 1.0 for validation and benchmark */
+    sl_episode_log_row *rows;     /* [capacity] */
+    int64_t *counters;            /* [SL_LOG_COUNTERS] n_rows; steps (<type>_steps); episodes (<type>_episodes); summarised
+                                     (rows the summaries have consumed); unmatched (queue entries that found no row) */
+    /* per env: the episode the env is PLAYING.  After an in-kernel reload scalars[e] describes the new episode, so the log
+     * remembers the old one, as the level schedule does. */
+    int32_t *cur_slot;            /* [B] */
+    int32_t *cur_required;        /* [B] */
+    int32_t *cur_episode;         /* [B] */
+    int64_t *last_row;            /* [B] global index of the env's latest row, -1: none */
+    const int32_t *reward_possible; /* [L] per pool slot, from the host */
+    double *value;                /* [SL_LOG_KEYS] summary_stats */
+    int64_t *count;               /* [SL_LOG_KEYS] summary_counts */
+    double *weight;               /* [SL_LOG_KEYS] the weight the key's NEXT value meets (the recurrence below) */
+} sl_episode_log;
+
+/* One launch after every step.  For every env e with out[e].done, in ascending e, row n_rows + rank(e) is written (rank: the
+ * number of done envs below e -- a row's place is a function of the done flags alone, no atomic's arrival order takes
+ * part): env = e, level = cur_slot[e], episode_idx = cur_episode[e], length / reward / success / times_up from out[e],
+ * training_steps = steps + e + 1 (the reference steps its envs in index order against one shared counter and the wrapper
+ * counts before it logs, :572-579), reward_possible = reward_possible[cur_slot[e]] (0 for a slot outside 0 .. L-1),
+ * reward_needed = cur_required[e], reward_frac as above, prev = last_row[e], flags = 0, the side-effect fields and score NaN.
+ * Then last_row[e] is the new row for those envs and, for EVERY env, cur_slot / cur_required / cur_episode =
+ * scalars[e].level_idx / required_points / episode_idx.  steps += B, episodes += n, n_rows += n.  Records of envs that are
+ * not done are not read beyond their done byte.  `out` takes 16-byte records (not sl_env_batch.out_compact).  Whoever
+ * reloads envs from outside the step sets their cur_* from the scalars itself. */
+int slhip_episode_log_harvest(const sl_episode_log *log, const sl_step_out *out, const sl_env_scalars *scalars, int B,
+                              void *stream);
+
+/* safelife_env.py:185-192's side_effect_weights: n <= SL_SE_MAX_KEYS pairs (cell, weight).  w(key) = 0.0 + the weights of
+ * the pairs whose cell equals key, in index order. */
+typedef struct sl_log_weights {
+    int32_t n;
+    int32_t reserved;
+    uint16_t cell[SL_SE_MAX_KEYS];
+    double weight[SL_SE_MAX_KEYS];
+} sl_log_weights;   /* 248 bytes */
+
+/* After a flush of the finished-episode queue and slhip_emd_batch: queue entry i < min(*count, capacity) carries
+ *   total[j] = 0.0 + sum_k w(keys[i,k]) * scores[i,k,j]   over the key slots k in index order, a product rounded before its
+ *   add; an empty slot (0xFFFF) contributes nothing and neither does a NaN score; NaN, NaN for an entry whose keys were cut
+ *   short (n_cells[i,0] < 0).
+ * It finds its row by walking `prev` from last_row[records[i].env] until env and episode_idx match.  The walk ends without
+ * a row at -1, at a row that has been overwritten (index < n_rows - capacity, or the stored index differs), after
+ * SL_LOG_MAX_HOPS rows, or at once for an env outside 0 .. B-1: the entry then counts into `unmatched`.  Otherwise the row gets
+ *   side_effects = total;  side_effects_frac = total[0] / m, m = total[1] if that is NaN, else max(total[1], 1.0)
+ *   (np.maximum);  speed = 1.0 - f64(length) / 1000.0;  score = (75.0 * reward_frac + 25.0 * speed) - 200.0 *
+ *   side_effects_frac;  flags |= SL_LOG_JOINED.
+ * scores double [C,SL_SE_MAX_KEYS,2], keys uint16 [C,SL_SE_MAX_KEYS], n_cells int32 [C,SL_SE_MAX_KEYS] as slhip_emd_batch
+ * and slhip_side_effects leave them. */
+int slhip_episode_log_join(const sl_episode_log *log, const sl_episode_queue *queue, const double *scores,
+                           const uint16_t *keys, const int32_t *n_cells, const sl_log_weights *weights, void *stream);
+
+/* log_scalars() :372-381 over rows [max(summarised, n_rows - capacity), n_rows) in row order, for each of the five keys:
+ * v = side_effects_frac, f64(length), reward_frac, success (0.0 / 1.0), score.  A value that is not finite is skipped for
+ * that key alone.  Otherwise, with w = weight[key]:
+ *   value = (v + w * value) / (1.0 + w);  count += 1;  w = f64(count) when polyak >= 1, else w = polyak * (1.0 + w).
+ * w starts at 0.0; the recurrence is the reference's p (1 - p^n) / (1 - p) without a pow, IEEE operations only.
+ * Then summarised = n_rows.  One workgroup: lane k walks key k's chain, the others stage the rows through LDS. */
+int slhip_episode_log_summaries(const sl_episode_log *log, void *stream);
+
+/* summarize_run_file() :719-762 over rows [max(first_row, n_rows - capacity, 0), n_rows) -> out double
+ * [SL_LOG_RUN_SUMMARY] (device):
+ *   0 rows n   1 success   2 avg_length   3 side_effects   4 reward   5 score      (means)
+ *   6 std side_effects   7 std reward   8 std score   9 mean, 10 std of length over the successful rows   11 their number
+ * Per row the side-effect totals go through np.nan_to_num (NaN -> 0, +-inf -> +-DBL_MAX; a row never joined has NaN
+ * totals), side_effects_frac and score are recomputed from them as in slhip_episode_log_join.  Every sum is ONE chain in
+ * ascending row order starting from 0.0 -- fixed by the row range alone, never by launch geometry or arrival; a mean is
+ * sum / f64(n), a standard deviation sqrt((sum of (x - mean) * (x - mean)) / f64(n)) in a second pass (np.std); n = 0 gives
+ * NaN.  One workgroup. */
+int slhip_episode_log_run_summary(const sl_episode_log *log, long long first_row, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

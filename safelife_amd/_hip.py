@@ -38,7 +38,12 @@ EXPORTS = (
     "slhip_rollout_compact_chunks", "slhip_rollout_compact", "slhip_rollout_gather",
     "slhip_schedule_draw", "slhip_schedule_required", "slhip_schedule_harvest", "slhip_schedule_curriculum",
     "slhip_schedule_required_multi", "slhip_schedule_harvest_multi",
+    "slhip_episode_log_harvest", "slhip_episode_log_join", "slhip_episode_log_summaries", "slhip_episode_log_run_summary",
 )
+LOG_JOINED, LOG_MAX_HOPS, LOG_RUN_SUMMARY = 1, 64, 12
+#: the summaries' keys, in the reference's order
+LOG_KEYS = ("side_effects", "length", "reward", "success", "score")
+LOG_COUNTERS = ("n_rows", "steps", "episodes", "summarised", "unmatched")
 SCHEDULE_MAX_GROUPS, SCHEDULE_MAX_LOOKBACK = 8, 1024
 SCHEDULE_BAD_PROBS = 1
 REWARD_F32, REWARD_F64 = 0, 1
@@ -190,6 +195,29 @@ class LevelScheduleMulti(C.Structure):
                 + [(n, C.c_void_p) for n in ("available", "reward_possible", "pool_agents", "out")])
 
 
+class EpisodeLogRow(C.Structure):
+    """struct sl_episode_log_row (96 bytes)"""
+    _fields_ = ([(n, C.c_int64) for n in ("index", "training_steps", "prev")]
+                + [(n, C.c_int32) for n in ("env", "level", "episode_idx", "length")]
+                + [("reward", C.c_float), ("reward_possible", C.c_int32), ("reward_needed", C.c_int32)]
+                + [(n, C.c_uint8) for n in ("success", "times_up", "flags", "reserved")]
+                + [("reward_frac", C.c_double), ("side_effects", C.c_double * 2), ("side_effects_frac", C.c_double),
+                   ("score", C.c_double)])
+
+
+class EpisodeLog(C.Structure):
+    """struct sl_episode_log (104 bytes)"""
+    _fields_ = ([("capacity", C.c_int64), ("B", C.c_int32), ("L", C.c_int32), ("polyak", C.c_double)]
+                + [(n, C.c_void_p) for n in ("rows", "counters", "cur_slot", "cur_required", "cur_episode", "last_row",
+                                             "reward_possible", "value", "count", "weight")])
+
+
+class LogWeights(C.Structure):
+    """struct sl_log_weights (248 bytes)"""
+    _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("cell", C.c_uint16 * SL_SE_MAX_KEYS),
+                ("weight", C.c_double * SL_SE_MAX_KEYS)]
+
+
 class EnvBatch(C.Structure):
     _fields_ = (
         [(n, C.c_int32) for n in ENV_SCALARS_HEAD]
@@ -305,6 +333,11 @@ def lib():
         L.slhip_schedule_curriculum.argtypes = [C.POINTER(LevelSchedule), _p, _p]
         L.slhip_schedule_required_multi.argtypes = [C.POINTER(LevelScheduleMulti), C.c_double, _p]
         L.slhip_schedule_harvest_multi.argtypes = [C.POINTER(LevelScheduleMulti), _p, C.c_int, _p]
+        L.slhip_episode_log_harvest.argtypes = [C.POINTER(EpisodeLog), _p, _p, C.c_int, _p]
+        L.slhip_episode_log_join.argtypes = [C.POINTER(EpisodeLog), C.POINTER(EpisodeQueue), _p, _p, _p,
+                                             C.POINTER(LogWeights), _p]
+        L.slhip_episode_log_summaries.argtypes = [C.POINTER(EpisodeLog), _p]
+        L.slhip_episode_log_run_summary.argtypes = [C.POINTER(EpisodeLog), C.c_longlong, _p, _p]
         L.slhip_obs_to_policy.argtypes = [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]
         L.slhip_gather_unique_id.argtypes = [_p]
         L.slhip_gather_init.argtypes = [_p, C.c_int, C.c_int, C.POINTER(_p)]

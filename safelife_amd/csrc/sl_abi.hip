@@ -1944,4 +1944,50 @@ int slhip_schedule_harvest_multi(const sl_level_schedule_multi *m, const sl_env_
     return err == hipSuccess ? SL_OK : hip_fail(err, "schedule_harvest_multi launch");
 }
 
+static int check_episode_log(const sl_episode_log *log, const char *who) {
+    if (!log) return fail(SL_E_ARG, std::string(who) + ": null log description");
+    if (log->B < 1 || log->L < 1) return fail(SL_E_SHAPE, std::string(who) + ": B and L must be at least 1");
+    if (log->capacity < log->B) return fail(SL_E_SHAPE, std::string(who) + ": capacity must be at least B");
+    if (!(log->polyak >= 0.0) || !(log->polyak - log->polyak == 0.0))
+        return fail(SL_E_SHAPE, std::string(who) + ": polyak must be finite and not negative");
+    if (!log->rows || !log->counters || !log->cur_slot || !log->cur_required || !log->cur_episode || !log->last_row ||
+        !log->reward_possible || !log->value || !log->count || !log->weight)
+        return fail(SL_E_ARG, std::string(who) + ": null pointer in the log description");
+    return SL_OK;
+}
+
+int slhip_episode_log_harvest(const sl_episode_log *log, const sl_step_out *out, const sl_env_scalars *scalars, int B,
+                              void *stream) {
+    if (int rc = check_episode_log(log, "episode_log_harvest")) return rc;
+    if (B != log->B) return fail(SL_E_SHAPE, "episode_log_harvest: B is not the log's B");
+    if (!out || !scalars) return fail(SL_E_ARG, "episode_log_harvest: null out / scalars");
+    const hipError_t err = sl::launch_episode_log_harvest(*log, out, scalars, B, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "episode_log_harvest launch");
+}
+
+int slhip_episode_log_join(const sl_episode_log *log, const sl_episode_queue *queue, const double *scores,
+                           const uint16_t *keys, const int32_t *n_cells, const sl_log_weights *weights, void *stream) {
+    if (int rc = check_episode_log(log, "episode_log_join")) return rc;
+    if (!queue || !weights) return fail(SL_E_ARG, "episode_log_join: null queue / weights");
+    if (queue->capacity < 1) return fail(SL_E_SHAPE, "episode_log_join: the queue has no slots");
+    if (weights->n < 0 || weights->n > SL_SE_MAX_KEYS) return fail(SL_E_SHAPE, "episode_log_join: weights.n outside 0..SL_SE_MAX_KEYS");
+    if (!queue->count || !queue->records || !scores || !keys || !n_cells)
+        return fail(SL_E_ARG, "episode_log_join: null count / records / scores / keys / n_cells");
+    const hipError_t err = sl::launch_episode_log_join(*log, *queue, scores, keys, n_cells, *weights, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "episode_log_join launch");
+}
+
+int slhip_episode_log_summaries(const sl_episode_log *log, void *stream) {
+    if (int rc = check_episode_log(log, "episode_log_summaries")) return rc;
+    const hipError_t err = sl::launch_episode_log_summaries(*log, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "episode_log_summaries launch");
+}
+
+int slhip_episode_log_run_summary(const sl_episode_log *log, long long first_row, double *out, void *stream) {
+    if (int rc = check_episode_log(log, "episode_log_run_summary")) return rc;
+    if (!out) return fail(SL_E_ARG, "episode_log_run_summary: null out");
+    const hipError_t err = sl::launch_episode_log_run_summary(*log, first_row, out, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "episode_log_run_summary launch");
+}
+
 }  // extern "C"

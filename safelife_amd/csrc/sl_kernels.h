@@ -127,6 +127,15 @@ hipError_t launch_schedule_curriculum(const sl_level_schedule &s, double *probs_
 hipError_t launch_schedule_required_multi(const sl_level_schedule_multi &m, double fraction, hipStream_t stream);
 hipError_t launch_schedule_harvest_multi(const sl_level_schedule_multi &m, const sl_env_scalars *scalars, int B,
                                          hipStream_t stream);
+// sl_episode_log.hip : the episode log -- a row per finished episode, the side-effect totals and the combined score joined
+// in from a flushed queue, the running summaries and the run summary
+hipError_t launch_episode_log_harvest(const sl_episode_log &log, const sl_step_out *out, const sl_env_scalars *scalars, int B,
+                                      hipStream_t stream);
+hipError_t launch_episode_log_join(const sl_episode_log &log, const sl_episode_queue &queue, const double *scores,
+                                   const uint16_t *keys, const int32_t *n_cells, const sl_log_weights &weights,
+                                   hipStream_t stream);
+hipError_t launch_episode_log_summaries(const sl_episode_log &log, hipStream_t stream);
+hipError_t launch_episode_log_run_summary(const sl_episode_log &log, long long first_row, double *out, hipStream_t stream);
 // envs [e_first, e_first + e_count) of the batch; actions / reward_t / done_t are indexed [t * tstride + e]
 // with the env's index in the whole batch
 // (sl_aql.hip dispatches the same kernel from queues of the library's own: PreparedStep below)

@@ -293,13 +293,19 @@ class SafeLifeVectorEnv(object):
                                    three in curriculum mode.  Only ``step()`` and ``reset()`` drive a schedule: ``rollout()``,
                                    ``step_async()``, ``step_slice()`` and the queue steppers raise ``ValueError``, and so
                                    does a refreshable pool.  None: nothing changes -- no launch, no allocation.
+    episode_log : episode_log.EpisodeLog or None
+                                   the arithmetic of the reference's SafeLifeLogger on the device: one kernel behind every
+                                   ``step()`` (behind the schedule's harvest, on the same stream) writes a row per finished
+                                   episode; ``episode_log.flush()`` joins the side-effect queue's totals in and folds the
+                                   rows into the running summaries.  Only ``step()`` and ``reset()`` drive a log, as with a
+                                   schedule.  None: nothing changes -- no launch, no allocation.
     """
 
     def __init__(self, pool, num_envs, *, time_limit=1000, remove_white_goals=True,
                  view_shape=(15, 15), output_channels=_DEFAULT_CHANNELS, auto_reset=True,
                  first_level=None, level_stride=1, env_offset=0, with_obs=True,
                  points_on_level_exit=1, wrappers=None, slices=1, episode_streams=True, side_effects=None,
-                 policy_layout=None, level_schedule=None):
+                 policy_layout=None, level_schedule=None, episode_log=None):
         import torch
         self.torch = torch
         if not isinstance(pool, LevelPool):
@@ -421,6 +427,9 @@ class SafeLifeVectorEnv(object):
                             keep=max(1, int(side_effects.get("keep", 2))))
             self._se["queue"] = self._new_queue()
             s.finished = self._se["queue"][0]
+        self.episode_log = episode_log
+        if episode_log is not None:         # one launch behind every step(): a row per finished episode
+            episode_log._attach(self)
         self._lib = _hip.lib()
         self._sref = C.byref(s)
         # slices: boundaries at multiples of 64 envs (keeps every slice 16-byte aligned for the row kernels)
@@ -741,6 +750,8 @@ class SafeLifeVectorEnv(object):
         _hip.check(rc)
         if sched is not None:
             sched._rewind(m)
+        if self.episode_log is not None:
+            self.episode_log._rewind(m)
         self._caller_ahead = True
         return self.obs
 
@@ -749,9 +760,15 @@ class SafeLifeVectorEnv(object):
     _SCHEDULE_QUEUES = ("the queue steppers run many steps on one successor table, nothing harvests their episode ends, and "
                         "the release-free recovery replays a logged pool_next whose content has changed since")
 
-    def _no_schedule(self, what, why):
+    _LOG_STREAMS = ("the step and the log's harvest are ordered on one stream; on the slice streams the harvest would miss "
+                    "episode ends")
+    _LOG_QUEUES = "the queue steppers run many steps and nothing harvests their episode ends"
+
+    def _no_schedule(self, what, why, log_why=None):
         if self.level_schedule is not None:
             raise ValueError("%s cannot drive a level schedule: %s (use step())" % (what, why))
+        if self.episode_log is not None:
+            raise ValueError("%s cannot drive an episode log: %s (use step())" % (what, log_why))
 
     def _actions(self, actions, shape):
         torch = self.torch
@@ -777,6 +794,8 @@ class SafeLifeVectorEnv(object):
         _hip.check(rc)
         if sched is not None:
             sched._after_step()
+        if self.episode_log is not None:
+            self.episode_log._after_step()
         self._caller_ahead = True
         self.steps_dispatched += 1
         return self.obs, self.reward, self.done, self.info
@@ -861,7 +880,7 @@ class SafeLifeVectorEnv(object):
         state since the previous sync is not valid."""
         if self._queues is not None:
             return
-        self._no_schedule("queues_open()", self._SCHEDULE_QUEUES)
+        self._no_schedule("queues_open()", self._SCHEDULE_QUEUES, self._LOG_QUEUES)
         self._rf_recover, self._rf_ckpt, self._queue_log = False, None, []
         B = self.num_envs
         n = int(slices if slices is not None else (len(queue_ids) if queue_ids is not None else
@@ -992,7 +1011,7 @@ class SafeLifeVectorEnv(object):
         ``defer=True`` (``slhip_queues_stage``, at most ``_hip.QUEUES_STAGE_MAX`` steps): the steps are written --
         argument blocks, packets -- but not handed to the device until ``queues_go()``; the action buffers must exist
         now, their contents only then.  What a hipGraph's instantiate / launch split does for a stream."""
-        self._no_schedule("step_queues()", self._SCHEDULE_QUEUES)
+        self._no_schedule("step_queues()", self._SCHEDULE_QUEUES, self._LOG_QUEUES)
         if isinstance(actions, int):
             ptr = actions
             if n_steps is None:
@@ -1100,7 +1119,7 @@ class SafeLifeVectorEnv(object):
         """One step per env, one launch per slice on the slice's own stream; nothing is fenced.  `actions`:
         a contiguous int32 device tensor [B] that is already complete (or ordered by ``fence()``), or its
         device address as an int.  Outputs are valid on the caller's stream after ``join()``."""
-        self._no_schedule("step_async()", self._SCHEDULE_STREAMS)
+        self._no_schedule("step_async()", self._SCHEDULE_STREAMS, self._LOG_STREAMS)
         if isinstance(actions, int):
             ptr = actions
         else:           # (a tensor: the checks step() makes through _actions(), without its conversions)
@@ -1127,7 +1146,7 @@ class SafeLifeVectorEnv(object):
         stream (``slice_stream(i)``); `actions`: the int32 device tensor [num_envs] of the whole batch (or its address) --
         only the slice's entries are read.  No fence: whoever writes the slice's actions and reads its outputs does so
         on the same stream (runner.PipelinedRunner), or orders itself against it."""
-        self._no_schedule("step_slice()", self._SCHEDULE_STREAMS)
+        self._no_schedule("step_slice()", self._SCHEDULE_STREAMS, self._LOG_STREAMS)
         if not 0 <= i < self.slices or self.slices < 2:
             raise ValueError("no such slice (construct the env with slices >= 2)")
         ptr = actions if isinstance(actions, int) else actions.data_ptr()
@@ -1155,7 +1174,8 @@ class SafeLifeVectorEnv(object):
     def rollout(self, actions, reward_out=None, done_out=None):
         """T steps in one launch.  actions: int [T,B].  Returns (reward[T,B], done[T,B])."""
         self._no_schedule("rollout()", "the successor table would stay constant across the launch's steps and the "
-                          "episodes that end inside it would not be harvested")
+                          "episodes that end inside it would not be harvested",
+                          "the episodes that end inside the launch would not be harvested")
         torch = self.torch
         T = int(actions.shape[0])
         a = self._actions(actions, (T, self.num_envs))
@@ -1181,7 +1201,8 @@ class SafeLifeVectorEnv(object):
         the kernel fill a send buffer directly.  ``compact``: 8-byte records there -- reward, done, success,
         times_up: ``sl_env_batch.out_compact`` -- (the env's own tensor always takes whole records)."""
         if out_ptr is not None:
-            self._no_schedule("set_step_outputs()", "the harvest reads the env's own step records")
+            self._no_schedule("set_step_outputs()", "the harvest reads the env's own step records",
+                              "the harvest reads the env's own step records")
         self.struct.out = self.t["out"].data_ptr() if out_ptr is None else int(out_ptr)
         self.struct.out_compact = 1 if (compact and out_ptr is not None) else 0
 
