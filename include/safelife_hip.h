@@ -334,6 +334,12 @@ int slhip_pool_write(const sl_env_batch *env, const sl_pool_rows *rows, void *st
  * consecutive envs; a block's first 32-bit word is its flag (1: the group steps on cached goal words). */
 size_t slhip_goal_cache_bytes(const sl_env_batch *env, int *boards_per_block);
 
+/* Which kernel family steps and resets this batch as described by *env: 1 = the row kernels, 0 = the size-generic kernels
+ * (no row kernel for the board shape, points outside int8 -- score_lut NULL --, more than 8 exit slots, a view too large
+ * for the fused policy-layout observation, unaligned arrays), < 0 = an error.  The answer is the whole batch's (launches
+ * that start at env 0 or at a multiple of 64 envs); nothing is launched. */
+int slhip_env_row_kernels(const sl_env_batch *env);
+
 /* SafeLifeEnv.reset() for the envs with mask[e] != 0 (mask NULL = all): an env that has never been loaded
  * takes pool level level_idx[e]; any other moves on to (level_idx[e] + level_stride) % L and counts an
  * episode, exactly as the in-kernel auto-reset does.  Writes the first observation. */
@@ -425,7 +431,11 @@ int slhip_env_step_range(const sl_env_batch *env, int first, int count, const in
 #define SL_QUEUES_SELFTEST_SWAP 2
 int slhip_queues_open(const sl_env_batch *env, int n_slices, const int32_t *bounds, int flags, void **handle);
 /* The same with slice i on queue queue_ids[i] (distinct, 0 to 7; NULL: slice i on queue i) -- for callers that leave
- * out a queue another kernel of theirs would hold up (slhip_gather_stream_shares). */
+ * out a queue another kernel of theirs would hold up (slhip_gather_stream_shares).
+ * SL_E_UNSUPPORTED also for a batch whose step kernel the queues cannot dispatch -- one that keeps private memory (it
+ * spills: the single-step kernels of 32x32 spawner pools), which these packets do not set up: found out here, when the
+ * queues are opened, never by a step.  The message then starts "AQL queues cannot dispatch this batch", where a runtime
+ * without queues to give says "AQL queues unavailable". */
 int slhip_queues_open_on(const sl_env_batch *env, int n_slices, const int32_t *bounds, const int32_t *queue_ids, int flags,
                          void **handle);
 /* Which of the queues 0 .. n_queues - 1 does a long one-wavefront kernel on HIP `stream` hold up (bit q of *mask)?

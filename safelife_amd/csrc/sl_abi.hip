@@ -536,6 +536,12 @@ static bool use_rowlane(const sl_env_batch *env, int e_first) {
     return false;
 }
 
+int slhip_env_row_kernels(const sl_env_batch *env) {
+    int rc = check_env(env);
+    if (rc) return rc;
+    return use_rowlane(env, 0) ? 1 : 0;
+}
+
 // One launch over envs [e_first, e_first + e_count).  actions / reward_t / done_t are indexed
 // [t * tstride + (env index in the whole batch)].
 static int rollout_range(const sl_env_batch *env, int e_first, int e_count, const int32_t *actions, int T, int tstride,
@@ -843,6 +849,20 @@ int slhip_queues_open_on(const sl_env_batch *env, int n_slices, const int32_t *b
     if (sl::aql_poisoned()) return fail(SL_E_HIP, "AQL queues: an earlier wait timed out on this device");
     if (const char *why = sl::aql_probe(sl::rowlane_probe_function()))
         return fail(SL_E_UNSUPPORTED, std::string("AQL queues unavailable: ") + why);
+    // the batch's own step kernel (one per batch, whichever slice): found out now, not by the first step's dispatch -- a
+    // caller that is refused here keeps to its streams
+    for (int i = 0; i < n_slices; ++i) {
+        if (bounds[i + 1] <= bounds[i]) continue;
+        const sl::Jump *jump;
+        if ((rc = jump_table(&jump))) return rc;
+        sl::PreparedStep step;
+        const hipError_t err = sl::launch_env_rollout_rowlane(*env, bounds[i], bounds[i + 1] - bounds[i], nullptr, 1, env->B, nullptr,
+                                                              nullptr, jump, nullptr, &step);
+        if (err != hipSuccess) return hip_fail(err, "AQL dispatch (prepare)");
+        if (const char *why = sl::aql_dispatchable(step.f, step.arg_bytes))
+            return fail(SL_E_UNSUPPORTED, std::string("AQL queues cannot dispatch this batch: ") + why);
+        break;
+    }
     StepQueues *c = new StepQueues;
     static std::atomic<uint32_t> serials{0};
     c->serial = ++serials;

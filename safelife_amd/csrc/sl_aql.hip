@@ -495,6 +495,26 @@ const char *aql_probe(hipFunction_t f) {
     return kernel_info(*d, f) ? nullptr : "HIP's kernels were not found in the HSA runtime's executables";
 }
 
+#ifndef SL_AQL_SCRATCH
+#define SL_AQL_SCRATCH 0        /* experiment: 1 = kernels with a private segment are dispatched too (the queue's scratch is the runtime's to set up) */
+#endif
+const char *aql_dispatchable(hipFunction_t f, size_t arg_bytes) {
+    static thread_local std::string why;
+    Device *d = current();
+    if (!d || !d->ok) return "AQL queues are not open";
+    if (!f) return "no HIP function handle to look up";
+    std::lock_guard<std::mutex> lock(d->mu);
+    const KernelInfo *k = kernel_info(*d, f);
+    if (!k) return "HIP's kernels were not found in the HSA runtime's executables";
+    if (arg_bytes > k->kernarg || k->kernarg > KARG_SLOT) return "the kernel's argument block does not fit the queues' argument slots";
+    if (k->priv != 0 && !SL_AQL_SCRATCH) {
+        why = "the step kernel of this batch keeps " + std::to_string((unsigned)k->priv) +
+              " bytes of private memory per lane (it spills), which the library's packets do not set up";
+        return why.c_str();
+    }
+    return nullptr;
+}
+
 namespace {
 // one kernel dispatch packet on `queue` (the caller holds d.mu); hd: the packet header, completion: its signal or {0}
 hipError_t emit(Device &d, const Hsa &h, int queue, hipFunction_t f, unsigned grid, unsigned threads, unsigned lds,
@@ -502,9 +522,6 @@ hipError_t emit(Device &d, const Hsa &h, int queue, hipFunction_t f, unsigned gr
                 const AqlPatch *patch = nullptr) {
     const KernelInfo *k = kernel_info(d, f);
     if (!k) return hipErrorNotFound;
-#ifndef SL_AQL_SCRATCH
-#define SL_AQL_SCRATCH 0        /* experiment: 1 = kernels with a private segment are dispatched too (the queue's scratch is the runtime's to set up) */
-#endif
     if (arg_bytes > k->kernarg || k->kernarg > KARG_SLOT || (k->priv != 0 && !SL_AQL_SCRATCH)) {
         // (never expected: say which -- a kernel that spills has private memory, which these packets do not set up)
         fprintf(stderr, "libsafelife_hip: AQL dispatch refused: argument block %zu bytes, kernel takes %u (slot %zu), private "

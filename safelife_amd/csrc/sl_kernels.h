@@ -167,6 +167,9 @@ hipError_t launch_env_rollout_rowlane(const sl_env_batch &env, int e_first, int 
 const char *aql_open(int n_queues);                 // null when usable, else why not
 const char *aql_probe(hipFunction_t f);             // can HIP's kernel `f` be found in the HSA executables? (null: yes)
 hipFunction_t rowlane_probe_function();             // any kernel of the library (sl_rowlane.hip)
+// can `f`, with an argument block of `arg_bytes`, be dispatched from the library's queues?  (null: yes; else why not --
+// a kernel that spills keeps private memory, which these packets do not set up)
+const char *aql_dispatchable(hipFunction_t f, size_t arg_bytes);
 // patch (optional): the argument block is `version` of `owner`'s (any non-zero ids the caller keeps unique); where the
 // queue's next argument slot already holds exactly that, only the 8-byte words at `offset[0..n)` are written again
 struct AqlPatch {

@@ -653,6 +653,14 @@ class SafeLifeVectorEnv(object):
             rf["fence"] = ("events", _EventSet(evs))
         return True
 
+    def row_kernels(self):
+        """True when the row kernels step and reset this batch, False when the size-generic kernels do (a board shape
+        without row kernels, points outside int8, more than 8 exit slots, a view too large for the fused policy layout)."""
+        rc = int(self._lib.slhip_env_row_kernels(self._sref))
+        if rc < 0:
+            _hip.check(rc)
+        return rc == 1
+
     def goal_cache_flags(self):
         """Per group of ``goal_cache_group`` consecutive envs: 1 where the group currently steps on cached goal words
         (host copy; None without a cache)."""
@@ -859,7 +867,9 @@ class SafeLifeVectorEnv(object):
 
     def queues_open(self, slices=None, release_free=None, queue_ids=None, recover=True):
         """Open one AQL queue per slice (default: SAFELIFE_QUEUE_SLICES or 4).  Raises SafeLifeHipError when the
-        batch or the runtime does not support it -- callers keep to step_async() then.
+        batch or the runtime does not support it -- callers keep to step_async() then.  (A batch whose step kernel
+        keeps private memory -- one that spills: the single-step kernels of 32x32 spawner pools -- is refused here too:
+        the queues' packets set up none.)
 
         ``queue_ids``: which of the library's queues the slices go onto (default: slice i on queue i) -- a driver whose
         own kernels would hold one of them up leaves that one out (``sharding.RewardGather.free_queues``).

@@ -2036,7 +2036,8 @@ def test_randomised_soak(seed):
     """tools/soak.py for a few seconds: random synthetic pools (shapes incl. 10x10 with 24 boards per
     workgroup, 0..8 exits, spawners, evolving goals, agent-less levels), random env options and wrapper
     settings, odd batch sizes -- device vs oracle on everything.  (Seed 1 is the run that caught the
-    wrapper-state write-back of workgroups holding more than 21 boards.)"""
+    wrapper-state write-back of workgroups holding more than 21 boards.)  The per-shape, per-variant guard of the
+    fused step is the deterministic matrix of tests/test_step_matrix_gpu.py; this is the randomised net behind it."""
     import subprocess, sys
     out = subprocess.check_output([sys.executable, os.path.join(util.REPO, "tools", "soak.py"), "6", str(seed)],
                                   cwd=util.REPO, stderr=subprocess.STDOUT).decode()
