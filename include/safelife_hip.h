@@ -1082,7 +1082,8 @@ int slhip_schedule_harvest_multi(const sl_level_schedule_multi *m, const sl_env_
  * nothing existing changes, so SL_ABI_VERSION stays where it is) ---------------------------------------------------------
  * The arithmetic of the reference's SafeLifeLogger (safelife_logger.py): log_episode() :262-354 with combined_score()
  * :671-716 per finished episode, the running summaries of log_scalars() :372-381, and summarize_run_file() :719-762 over the
- * rows.  Files, tensorboard, wandb and video stay with the host.  Single-agent batches only.
+ * rows.  Files, tensorboard, wandb and video stay with the host.  These four entry points serve single-agent batches; the
+ * four _multi ones further down serve batches with several agents per env.
  *
  * A finished episode becomes a ROW.  Row i (counted from the log's start) lives at rows[i % capacity]; a row is valid while
  * i >= n_rows - capacity and rows[i % capacity].index == i.  All float64 arithmetic is unfused, every operation rounded on
@@ -1186,6 +1187,101 @@ int slhip_episode_log_summaries(const sl_episode_log *log, void *stream);
  * sum / f64(n), a standard deviation sqrt((sum of (x - mean) * (x - mean)) / f64(n)) in a second pass (np.std); n = 0 gives
  * NaN.  One workgroup. */
 int slhip_episode_log_run_summary(const sl_episode_log *log, long long first_row, double *out, void *stream);
+
+/* ---- the episode log for envs with several agents (additive again: four symbols, one log struct and one row layout beside
+ * the single-agent ones, which stay byte for byte; SL_ABI_VERSION stays where it is) -----------------------------------------
+ * What SafeLifeLogger does when info['episode'] holds arrays over the agents (safelife_logger.py:289-291, :319-328):
+ *   - SafeLifeLogWrapper counts one <type>_steps per env step and logs once, on the step where np.all(done) (:572-579), so
+ *     training_steps = steps + e + 1 and steps += B carry over;
+ *   - length, reward, success, reward_possible, reward_needed, reward_frac and score are per agent; combined_score() sees one
+ *     side_effects['total'] per episode, so the two totals and side_effects_frac are per row;
+ *   - log_scalars() gets name-length, name-reward, name-success and name-score per agent, name = game.agent_names[i]; tb_data
+ *     is a dict, so of two agents of one level with the same name the LAST one's values stay; tb_data['side_effects'] is a
+ *     shape-(1,) array, fails np.isscalar and is never summarised.  (reward_frac_needed stays with the caller, as for the
+ *     single-agent log.)
+ * A row is a header followed by n_agents agent records: SL_LOG_ROW_MULTI_BYTES(A) bytes, the stride fixed by A when the log
+ * is allocated -- 144 bytes for two agents where a stride of SL_MAX_AGENTS would take 384 (the two summary kernels stream
+ * whole rows and the ring holds `capacity` of them).  Row i lives at rows + (i % capacity) * SL_LOG_ROW_MULTI_BYTES(A) and is
+ * valid under the single-agent rule. */
+typedef struct sl_episode_log_agent { /* 40 bytes */
+    int32_t length;               /* info['episode']['length'][a] */
+    float reward;                 /* info['episode']['reward'][a] */
+    int32_t reward_possible;      /* (initial_available_points() + points_on_level_exit)[a] */
+    int32_t reward_needed;        /* required_points()[a] of the episode */
+    uint8_t success, times_up;
+    uint8_t name;                 /* the agent's name id in 0 .. n_names-1; SL_LOG_NO_NAME for a slot outside 0 .. L-1 */
+    uint8_t reserved[5];
+    double reward_frac;           /* f64(reward) / f64(max(reward_possible, 1)) */
+    double score;                 /* (75 reward_frac + 25 (1 - f64(length) / 1000)) - 200 side_effects_frac; NaN until joined */
+} sl_episode_log_agent;
+typedef struct sl_episode_log_row_multi { /* 64 bytes, then sl_episode_log_agent[n_agents] */
+    int64_t index, training_steps, prev;   /* as sl_episode_log_row */
+    int32_t env, level, episode_idx;
+    uint8_t flags;                /* SL_LOG_JOINED */
+    uint8_t n_agents;
+    uint8_t reserved[2];
+    double side_effects[2];       /* the episode's weighted totals (agent, inaction); NaN until joined */
+    double side_effects_frac;     /* one per row; NaN until joined */
+} sl_episode_log_row_multi;
+#define SL_LOG_ROW_MULTI_BYTES(A) (64 + 40 * (A))
+#define SL_LOG_MAX_NAMES 16       /* distinct agent names of a pool */
+#define SL_LOG_NO_NAME 0xFF
+#define SL_LOG_MULTI_KEYS 4       /* summaries per name, in the reference's order: length, reward, success, score */
+
+typedef struct sl_episode_log_multi { /* 120 bytes; every pointer is device memory */
+    int64_t capacity;             /* rows of the ring, >= B */
+    int32_t B, L;
+    int32_t n_agents;             /* A, 1 .. SL_MAX_AGENTS */
+    int32_t n_names;              /* 1 .. SL_LOG_MAX_NAMES */
+    double polyak;
+    void *rows;                   /* [capacity] rows of SL_LOG_ROW_MULTI_BYTES(n_agents) bytes */
+    int64_t *counters;            /* [SL_LOG_COUNTERS], as sl_episode_log */
+    int32_t *cur_slot;            /* [B] the episode the env is PLAYING, as sl_episode_log */
+    int32_t *cur_required;        /* [B, A] sl_agent_state.required_points of that episode: after an in-kernel reload the agent
+                                     state describes the next one, which is why the log remembers */
+    int32_t *cur_episode;         /* [B] */
+    int64_t *last_row;            /* [B] */
+    const int32_t *reward_possible; /* [L, A] per pool slot and agent, from the host (sl_level_schedule_multi's) */
+    const uint8_t *name_id;       /* [L, A] per pool slot and agent: index into the host's list of the pool's distinct names */
+    double *value;                /* [SL_LOG_MAX_NAMES, SL_LOG_MULTI_KEYS] summary_stats of "<name>-<key>" */
+    int64_t *count;               /* [SL_LOG_MAX_NAMES, SL_LOG_MULTI_KEYS] summary_counts */
+    double *weight;               /* [SL_LOG_MAX_NAMES, SL_LOG_MULTI_KEYS] */
+} sl_episode_log_multi;
+
+/* slhip_episode_log_harvest for records [B, A].  Env e has finished on this step when ALL of out[e][0 .. A) have done != 0
+ * (slhip_schedule_harvest_multi's rule: the step on which the multi-agent kernel reloads the env; an agent that left earlier
+ * keeps done = 1 and its episode accumulators in `out` on every later step, so an episode files exactly one row, on the step
+ * of its last agent).  For every finished env, in ascending e, row n_rows + rank(e) -- rank: the number of finished envs below
+ * e, a function of the all-done flags alone -- gets the header of slhip_episode_log_harvest (flags = 0, the totals and
+ * side_effects_frac NaN) and per agent a: length / reward / success / times_up from out[e][a], reward_possible =
+ * reward_possible[cur_slot[e]][a] and name = name_id[cur_slot[e]][a] (0 and SL_LOG_NO_NAME for a slot outside 0 .. L-1),
+ * reward_needed = cur_required[e][a], reward_frac as above, score NaN.  Then last_row[e] is the new row for those envs and,
+ * for EVERY env, cur_slot / cur_episode = scalars[e].level_idx / episode_idx and cur_required[e][a] =
+ * agents[e][a].required_points.  steps += B, episodes += n, n_rows += n.  Records of envs that have not finished are not read
+ * beyond their done bytes.  The env must reload finished envs inside the step (auto_reset): one that stayed all-done would
+ * file a row per step where the reference files one.  One launch. */
+int slhip_episode_log_harvest_multi(const sl_episode_log_multi *log, const sl_step_out *out, const sl_agent_state *agents,
+                                    const sl_env_scalars *scalars, int B, void *stream);
+
+/* slhip_episode_log_join for the multi-agent queue, which files one entry per env episode: the totals, the walk along `prev`
+ * (SL_LOG_MAX_HOPS, the same validity checks, the same `unmatched` counter) and side_effects_frac are the single-agent
+ * join's; then, per agent, score[a] from reward_frac[a], length[a] and the row's one fraction; flags |= SL_LOG_JOINED. */
+int slhip_episode_log_join_multi(const sl_episode_log_multi *log, const sl_episode_queue *queue, const double *scores,
+                                 const uint16_t *keys, const int32_t *n_cells, const sl_log_weights *weights, void *stream);
+
+/* log_scalars() over rows [max(summarised, n_rows - capacity), n_rows) in row order.  Key (n, q), n < n_names, q of length,
+ * reward, success, score: a row takes part if one of its agents has name n; its value is that of the LAST such agent (v =
+ * f64(length), reward_frac, 0.0 / 1.0, score); a value that is not finite is skipped for that key alone (an earlier agent of
+ * the name does not stand in).  The recurrence, w and count are slhip_episode_log_summaries'.  Then summarised = n_rows.
+ * One workgroup: the 64 lanes of wave 0 walk one chain each out of LDS while the other waves stage the next 64 rows -- per
+ * row and agent four values and the name id, so the staging grows with A and not with the number of keys. */
+int slhip_episode_log_summaries_multi(const sl_episode_log_multi *log, void *stream);
+
+/* summarize_run_file() over [N, A] arrays: the twelve outputs of slhip_episode_log_run_summary, where success, avg_length,
+ * reward, score and the successful length run over the N * A (row, agent) entries -- each sum ONE chain in ascending (row,
+ * agent) order starting from 0.0 -- and side_effects over the N rows; out[0] is N, out[11] the number of successful
+ * entries.  The totals go through np.nan_to_num and side_effects_frac and every score are recomputed, two passes. */
+int slhip_episode_log_run_summary_multi(const sl_episode_log_multi *log, long long first_row, double *out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -39,8 +39,13 @@ EXPORTS = (
     "slhip_schedule_draw", "slhip_schedule_required", "slhip_schedule_harvest", "slhip_schedule_curriculum",
     "slhip_schedule_required_multi", "slhip_schedule_harvest_multi",
     "slhip_episode_log_harvest", "slhip_episode_log_join", "slhip_episode_log_summaries", "slhip_episode_log_run_summary",
+    "slhip_episode_log_harvest_multi", "slhip_episode_log_join_multi", "slhip_episode_log_summaries_multi",
+    "slhip_episode_log_run_summary_multi",
 )
 LOG_JOINED, LOG_MAX_HOPS, LOG_RUN_SUMMARY = 1, 64, 12
+LOG_MAX_NAMES, LOG_NO_NAME = 16, 0xFF
+#: the per-name summaries' keys of a multi-agent log, in the reference's order
+LOG_MULTI_KEYS = ("length", "reward", "success", "score")
 #: the summaries' keys, in the reference's order
 LOG_KEYS = ("side_effects", "length", "reward", "success", "score")
 LOG_COUNTERS = ("n_rows", "steps", "episodes", "summarised", "unmatched")
@@ -212,6 +217,19 @@ class EpisodeLog(C.Structure):
                                              "reward_possible", "value", "count", "weight")])
 
 
+class EpisodeLogMulti(C.Structure):
+    """struct sl_episode_log_multi (120 bytes)"""
+    _fields_ = ([("capacity", C.c_int64), ("B", C.c_int32), ("L", C.c_int32), ("n_agents", C.c_int32),
+                 ("n_names", C.c_int32), ("polyak", C.c_double)]
+                + [(n, C.c_void_p) for n in ("rows", "counters", "cur_slot", "cur_required", "cur_episode", "last_row",
+                                             "reward_possible", "name_id", "value", "count", "weight")])
+
+
+def log_row_multi_bytes(n_agents):
+    """SL_LOG_ROW_MULTI_BYTES(A): a 64-byte header and 40 bytes per agent."""
+    return 64 + 40 * int(n_agents)
+
+
 class LogWeights(C.Structure):
     """struct sl_log_weights (248 bytes)"""
     _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("cell", C.c_uint16 * SL_SE_MAX_KEYS),
@@ -340,6 +358,11 @@ def lib():
                                              C.POINTER(LogWeights), _p]
         L.slhip_episode_log_summaries.argtypes = [C.POINTER(EpisodeLog), _p]
         L.slhip_episode_log_run_summary.argtypes = [C.POINTER(EpisodeLog), C.c_longlong, _p, _p]
+        L.slhip_episode_log_harvest_multi.argtypes = [C.POINTER(EpisodeLogMulti), _p, _p, _p, C.c_int, _p]
+        L.slhip_episode_log_join_multi.argtypes = [C.POINTER(EpisodeLogMulti), C.POINTER(EpisodeQueue), _p, _p, _p,
+                                                   C.POINTER(LogWeights), _p]
+        L.slhip_episode_log_summaries_multi.argtypes = [C.POINTER(EpisodeLogMulti), _p]
+        L.slhip_episode_log_run_summary_multi.argtypes = [C.POINTER(EpisodeLogMulti), C.c_longlong, _p, _p]
         L.slhip_obs_to_policy.argtypes = [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]
         L.slhip_gather_unique_id.argtypes = [_p]
         L.slhip_gather_init.argtypes = [_p, C.c_int, C.c_int, C.POINTER(_p)]

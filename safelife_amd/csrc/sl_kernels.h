@@ -136,6 +136,16 @@ hipError_t launch_episode_log_join(const sl_episode_log &log, const sl_episode_q
                                    hipStream_t stream);
 hipError_t launch_episode_log_summaries(const sl_episode_log &log, hipStream_t stream);
 hipError_t launch_episode_log_run_summary(const sl_episode_log &log, long long first_row, double *out, hipStream_t stream);
+// the same for envs with several agents: rows of a header and A agent records, a row when ALL agents of an env are done
+hipError_t launch_episode_log_harvest_multi(const sl_episode_log_multi &log, const sl_step_out *out,
+                                            const sl_agent_state *agents, const sl_env_scalars *scalars, int B,
+                                            hipStream_t stream);
+hipError_t launch_episode_log_join_multi(const sl_episode_log_multi &log, const sl_episode_queue &queue, const double *scores,
+                                         const uint16_t *keys, const int32_t *n_cells, const sl_log_weights &weights,
+                                         hipStream_t stream);
+hipError_t launch_episode_log_summaries_multi(const sl_episode_log_multi &log, hipStream_t stream);
+hipError_t launch_episode_log_run_summary_multi(const sl_episode_log_multi &log, long long first_row, double *out,
+                                                hipStream_t stream);
 // envs [e_first, e_first + e_count) of the batch; actions / reward_t / done_t are indexed [t * tstride + e]
 // with the env's index in the whole batch
 // (sl_aql.hip dispatches the same kernel from queues of the library's own: PreparedStep below)

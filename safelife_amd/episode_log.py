@@ -16,8 +16,12 @@ running summaries (``slhip_episode_log_summaries``); ``run_summary()`` is ``summ
 tests/episode_log_ref.py.  Files, tensorboard, wandb, video and ``reward_frac_needed`` stay with the caller: ``records()``
 hands over what the JSON log holds.
 
-Single-agent ``SafeLifeVectorEnv`` only.  NOT done: multi-agent logging -- per-agent arrays, a log entry when all agents are
-done, and the ``name-`` prefixed keys.
+``EpisodeLog`` serves a single-agent ``SafeLifeVectorEnv``.  ``MultiAgentEpisodeLog`` serves a
+``SafeLifeMultiAgentVectorEnv`` with the same surface: one row per env episode, filed on the step where all its agents are
+done (``slhip_episode_log_harvest_multi``), per-agent ``length`` / ``reward`` / ``success`` / ``score`` beside the row's one
+side-effect fraction, and running summaries under the reference's ``<agent name>-`` prefixed keys
+(``slhip_episode_log_join_multi`` / ``_summaries_multi`` / ``_run_summary_multi``; restated in
+tests/episode_log_multi_ref.py).
 """
 import ctypes as C
 
@@ -36,6 +40,29 @@ _ROW_WORDS = ROW_DTYPE.itemsize // 8
 _DEFAULT_POLYAK = {"training": 0.99}
 RUN_SUMMARY_FIELDS = ("rows", "success", "avg_length", "side_effects", "reward", "score", "side_effects_std", "reward_std",
                       "score_std", "successful_length", "successful_length_std", "successes")
+
+
+def _common_arguments(num_envs, capacity, episode_type, summary_polyak, side_effect_weights):
+    """The checks both logs share -> num_envs, capacity, episode_type, summary_polyak, the weights' dict and their
+    ``struct sl_log_weights``."""
+    num_envs, capacity, episode_type = int(num_envs), int(capacity), str(episode_type)
+    if num_envs < 1:
+        raise ValueError("num_envs must be at least 1")
+    if capacity < num_envs:
+        raise ValueError("capacity (%d) must be at least num_envs (%d): one step can end every env's episode"
+                         % (capacity, num_envs))
+    p = _DEFAULT_POLYAK.get(episode_type, 1.0) if summary_polyak is None else float(summary_polyak)
+    if not (np.isfinite(p) and p >= 0.0):
+        raise ValueError("summary_polyak must be finite and not negative, got %r" % (summary_polyak,))
+    from .side_effects import name_to_cell
+    weights = dict(side_effect_weights or {})
+    if len(weights) > _hip.SL_SE_MAX_KEYS:
+        raise ValueError("at most %d side-effect weights, got %d" % (_hip.SL_SE_MAX_KEYS, len(weights)))
+    w = _hip.LogWeights()
+    w.n = len(weights)
+    for j, (name, weight) in enumerate(weights.items()):
+        w.cell[j], w.weight[j] = name_to_cell(name), float(weight)
+    return num_envs, capacity, episode_type, p, weights, w
 
 
 class EpisodeLog(object):
@@ -59,27 +86,10 @@ class EpisodeLog(object):
             raise TypeError("pool must be a LevelPool")
         if int(pool.n_agents) > 1:
             raise ValueError("the episode log serves a single-agent SafeLifeVectorEnv: this pool has %d agents per level "
-                             "(multi-agent logging is not done)" % pool.n_agents)
+                             "(MultiAgentEpisodeLog serves a SafeLifeMultiAgentVectorEnv)" % pool.n_agents)
         self.pool = pool
-        self.num_envs, self.capacity = int(num_envs), int(capacity)
-        if self.num_envs < 1:
-            raise ValueError("num_envs must be at least 1")
-        if self.capacity < self.num_envs:
-            raise ValueError("capacity (%d) must be at least num_envs (%d): one step can end every env's episode"
-                             % (self.capacity, self.num_envs))
-        self.episode_type = str(episode_type)
-        p = _DEFAULT_POLYAK.get(self.episode_type, 1.0) if summary_polyak is None else float(summary_polyak)
-        if not (np.isfinite(p) and p >= 0.0):
-            raise ValueError("summary_polyak must be finite and not negative, got %r" % (summary_polyak,))
-        self.summary_polyak = p
-        from .side_effects import name_to_cell
-        self.side_effect_weights = dict(side_effect_weights or {})
-        if len(self.side_effect_weights) > _hip.SL_SE_MAX_KEYS:
-            raise ValueError("at most %d side-effect weights, got %d" % (_hip.SL_SE_MAX_KEYS, len(self.side_effect_weights)))
-        w = self._weights = _hip.LogWeights()
-        w.n = len(self.side_effect_weights)
-        for j, (name, weight) in enumerate(self.side_effect_weights.items()):
-            w.cell[j], w.weight[j] = name_to_cell(name), float(weight)
+        (self.num_envs, self.capacity, self.episode_type, self.summary_polyak, self.side_effect_weights,
+         self._weights) = _common_arguments(num_envs, capacity, episode_type, summary_polyak, side_effect_weights)
         # per slot: agent 0's available points (safelife_game.py:696-709), as LevelSchedule computes them
         self.available = np.zeros(pool.n_slots, np.int32)
         for k, lv in enumerate(pool.levels):
@@ -228,6 +238,247 @@ class EpisodeLog(object):
         res = dict(zip(RUN_SUMMARY_FIELDS, vals.tolist()))
         res["rows"], res["successes"] = int(vals[0]), int(vals[11])
         return res
+
+
+def multi_row_dtype(n_agents):
+    """numpy's view of ``struct sl_episode_log_row_multi`` followed by its ``n_agents`` ``sl_episode_log_agent`` records
+    (``SL_LOG_ROW_MULTI_BYTES``)."""
+    agent = np.dtype([("length", "<i4"), ("reward", "<f4"), ("reward_possible", "<i4"), ("reward_needed", "<i4"),
+                      ("success", "u1"), ("times_up", "u1"), ("name", "u1"), ("reserved", "u1", (5,)),
+                      ("reward_frac", "<f8"), ("score", "<f8")])
+    row = np.dtype([("index", "<i8"), ("training_steps", "<i8"), ("prev", "<i8"), ("env", "<i4"), ("level", "<i4"),
+                    ("episode_idx", "<i4"), ("flags", "u1"), ("n_agents", "u1"), ("reserved", "u1", (2,)),
+                    ("side_effects", "<f8", (2,)), ("side_effects_frac", "<f8"), ("agents", agent, (int(n_agents),))])
+    assert row.itemsize == _hip.log_row_multi_bytes(n_agents)
+    return row
+
+
+class MultiAgentEpisodeLog(object):
+    """
+    The episode log for a ``SafeLifeMultiAgentVectorEnv``: what ``SafeLifeLogger`` does when ``info['episode']`` holds
+    arrays over the agents (safelife_logger.py:289-291, :319-328).  A row per env EPISODE, filed on the step where all its
+    agents are done; ``length``, ``reward``, ``success``, ``reward_possible``, ``reward_needed``, ``reward_frac`` and ``score``
+    per agent, the side-effect totals and their fraction per row; running summaries ``<name>-length | -reward | -success |
+    -score`` per distinct agent name, where of two agents of one level with the same name the last one counts (``tb_data``
+    is a dict) and a key is only moved by episodes whose level has an agent of that name.  There is no ``side_effects``
+    summary: the reference hands ``log_scalars`` a shape-(1,) array there, which it skips.
+
+    pool : LevelPool(levels, n_agents=A)        a pool with one agent per level logs arrays and ``agent0-`` keys too
+    num_envs, capacity, episode_type, summary_polyak, side_effect_weights : as ``EpisodeLog``
+    agent_names : one list of A names per pool slot, or None: ``agent0 .. agent{A-1}`` for every slot (what
+                  ``safelife_amd.game`` names them); at most 16 distinct names
+
+    Attach with ``SafeLifeMultiAgentVectorEnv(pool, ..., episode_log=log)`` (``auto_reset=True``); the surface is
+    ``EpisodeLog``'s.
+    """
+
+    def __init__(self, pool, num_envs, capacity, episode_type="training", summary_polyak=None, side_effect_weights=None,
+                 agent_names=None):
+        if not isinstance(pool, LevelPool):
+            raise TypeError("pool must be a LevelPool")
+        A = self.n_agents = int(pool.n_agents)
+        if not 1 <= A <= _hip.SL_MAX_AGENTS:
+            raise ValueError("the pool must have 1 to %d agents per level, not %d" % (_hip.SL_MAX_AGENTS, A))
+        self.pool = pool
+        (self.num_envs, self.capacity, self.episode_type, self.summary_polyak, self.side_effect_weights,
+         self._weights) = _common_arguments(num_envs, capacity, episode_type, summary_polyak, side_effect_weights)
+        L = pool.n_slots
+        if agent_names is None:
+            agent_names = [["agent%d" % a for a in range(A)]] * L
+        agent_names = [[str(n) for n in names] for names in agent_names]
+        if len(agent_names) != L or any(len(names) != A for names in agent_names):
+            raise ValueError("agent_names must hold one list of %d names for each of the pool's %d slots" % (A, L))
+        self.agent_names = agent_names
+        self.names = []                     # the distinct names, in order of appearance
+        self.name_id = np.zeros((L, A), np.uint8)
+        for k, names in enumerate(agent_names):
+            for a, name in enumerate(names):
+                if name not in self.names:
+                    self.names.append(name)
+                self.name_id[k, a] = min(self.names.index(name), _hip.LOG_NO_NAME)
+        if len(self.names) > _hip.LOG_MAX_NAMES:
+            raise ValueError("at most %d distinct agent names, got %d" % (_hip.LOG_MAX_NAMES, len(self.names)))
+        # per slot and agent: the agent's own table against the level's counts (safelife_game.py:696-709), as LevelSchedule
+        self.available = np.zeros((L, A), np.int32)
+        for k, lv in enumerate(pool.levels):
+            colors = initial_colors(lv.board)
+            for a in range(A):
+                idx = pool.pool_agent_table_idx[k, a] if A > 1 else pool.pool_table_idx[k]
+                self.available[k, a] = available_points(pool.points_table[idx].astype(np.int64), pool.initial_counts[k], colors)
+        self.row_dtype = multi_row_dtype(A)
+        self.env = None
+        self.t = None
+
+    def reward_possible(self, points_on_level_exit=1):
+        """What the logger records as ``reward_possible`` (:286-287), int32 [L, A]."""
+        return (self.available.astype(np.int64) + int(points_on_level_exit)).astype(np.int32)
+
+    # ---- device side
+
+    def allocate(self, torch, device, points_on_level_exit=1):
+        """The device state (``SafeLifeMultiAgentVectorEnv`` calls this through ``_attach``; a caller with step records of
+        its own calls it and ``harvest()`` itself)."""
+        B, A, cap, dev = self.num_envs, self.n_agents, self.capacity, device
+        n_keys = _hip.LOG_MAX_NAMES * len(_hip.LOG_MULTI_KEYS)
+        self.torch = torch
+        t = self.t = {}
+        t["rows"] = torch.zeros((cap, self.row_dtype.itemsize // 8), dtype=torch.int64, device=dev)
+        t["rows"][:, 0] = -1                        # (no row's index)
+        # counters | counts | values | weights in one buffer: summary() is one host visit
+        t["state"] = torch.zeros(5 + 3 * n_keys, dtype=torch.int64, device=dev)
+        t["counters"], t["count"] = t["state"][0:5], t["state"][5:5 + n_keys]
+        t["value"] = t["state"][5 + n_keys:5 + 2 * n_keys].view(torch.float64)
+        t["weight"] = t["state"][5 + 2 * n_keys:].view(torch.float64)
+        t["cur_slot"] = torch.zeros(B, dtype=torch.int32, device=dev)
+        t["cur_required"] = torch.zeros((B, A), dtype=torch.int32, device=dev)
+        t["cur_episode"] = torch.zeros(B, dtype=torch.int32, device=dev)
+        t["last_row"] = torch.full((B,), -1, dtype=torch.int64, device=dev)
+        t["reward_possible"] = torch.from_numpy(self.reward_possible(points_on_level_exit)).to(dev)
+        t["name_id"] = torch.from_numpy(self.name_id).to(dev)
+        t["run_summary"] = torch.zeros(_hip.LOG_RUN_SUMMARY, dtype=torch.float64, device=dev)
+        s = self.struct = _hip.EpisodeLogMulti()
+        s.capacity, s.B, s.L, s.n_agents, s.n_names, s.polyak = cap, B, self.pool.n_slots, A, len(self.names), self.summary_polyak
+        for name in ("rows", "counters", "cur_slot", "cur_required", "cur_episode", "last_row", "reward_possible", "name_id",
+                     "value", "count", "weight"):
+            setattr(s, name, t[name].data_ptr())
+        self._sref = C.byref(s)
+        self._lib = _hip.lib()
+        return t
+
+    def _attach(self, env):
+        if self.env is not None:
+            raise ValueError("this MultiAgentEpisodeLog already serves an env")
+        if env.pool is not self.pool:
+            raise ValueError("the episode log was built for another pool")
+        if env.num_envs != self.num_envs:
+            raise ValueError("the episode log was built for %d envs, the env has %d" % (self.num_envs, env.num_envs))
+        self.allocate(env.torch, env.device, env.base.struct.exit_points)
+        self.env = env
+        self._rewind()
+
+    def _rewind(self, mask=None):
+        """After the envs (those with mask != 0) have been reset from outside the step: their episodes start over."""
+        env, cols, t, torch = self.env, _hip.SCALAR_COLS, self.t, self.torch
+        sc = env.base.t["scalars"]
+        now = {"cur_slot": sc[:, cols["level_idx"]], "cur_episode": sc[:, cols["episode_idx"]],
+               "cur_required": env.t["agents"][:, :, _hip.AGENT_COLS["required_points"]]}
+        for name, value in now.items():
+            sel = None if mask is None else (mask != 0 if value.dim() == 1 else (mask != 0)[:, None])
+            t[name].copy_(value if sel is None else torch.where(sel, value, t[name]))
+        if mask is None:
+            t["last_row"].fill_(-1)
+        else:
+            t["last_row"].masked_fill_(mask != 0, -1)
+
+    def harvest(self, out, agents, scalars):
+        """One launch on the current stream: rows for the envs ALL of whose records in `out` (int32 [B,A,4], ``struct
+        sl_step_out``) say done; `agents` int32 [B,A,12] and `scalars` int32 [B,16] as the step left them."""
+        rc = self._lib.slhip_episode_log_harvest_multi(self._sref, _hip.ptr(out), _hip.ptr(agents), _hip.ptr(scalars),
+                                                       self.num_envs, _hip.current_stream_ptr())
+        if rc:
+            _hip.check(rc)
+
+    def _after_step(self):
+        self.harvest(self.env.t["out"], self.env.t["agents"], self.env.base.t["scalars"])
+
+    def join(self, count, records, scores, keys, n_cells):
+        """The join of one flushed queue (one entry per env episode; the tensors of ``EpisodeLog.join``)."""
+        q = _hip.EpisodeQueue()
+        q.capacity, q.env_base = int(records.shape[0]), 0
+        q.count, q.records = count.data_ptr(), records.data_ptr()
+        _hip.check(self._lib.slhip_episode_log_join_multi(self._sref, C.byref(q), _hip.ptr(scores), _hip.ptr(keys),
+                                                          _hip.ptr(n_cells), C.byref(self._weights),
+                                                          _hip.current_stream_ptr()))
+
+    def summarise(self):
+        """Folds the rows not yet consumed into the running summaries, on the current stream."""
+        _hip.check(self._lib.slhip_episode_log_summaries_multi(self._sref, _hip.current_stream_ptr()))
+
+    def flush(self):
+        """On the caller's stream: with a side-effect queue on the env, its ``side_effects_flush()``, ``scores_all()`` and
+        the join; then the summaries.  Returns the ``SideEffectBatch`` or None.  Without a queue the scores never count."""
+        env, batch = self.env, None
+        if env is None:
+            raise ValueError("the episode log is not attached to an env")
+        if env.base._se is not None:
+            batch = env.side_effects_flush()
+            emd = batch.scores_all()
+            self.join(batch.count, batch.rec_tensor, emd["scores"], batch.keys, emd["n_cells"])
+        self.summarise()
+        return batch
+
+    # ---- host side: each of these is one visit
+
+    def _state(self):
+        if self.t is None:
+            raise ValueError("the episode log has no device state yet: hand it to "
+                             "SafeLifeMultiAgentVectorEnv(episode_log=...)")
+        raw = self.t["state"].cpu().numpy()
+        n = _hip.LOG_MAX_NAMES * len(_hip.LOG_MULTI_KEYS)
+        return (dict(zip(_hip.LOG_COUNTERS, raw[0:5].tolist())), raw[5:5 + n].copy(),
+                raw[5 + n:5 + 2 * n].copy().view(np.float64), raw[5 + 2 * n:].copy().view(np.float64))
+
+    def counters(self):
+        """``n_rows``, ``steps``, ``episodes``, ``summarised``, ``unmatched``."""
+        return self._state()[0]
+
+    def summary(self):
+        """``{"training/agent0-length": ..., ...}`` for the keys that have met a finite value, name by name in the order
+        the pool first shows them, plus ``training/steps`` and ``training/episodes``."""
+        counters, count, value, _ = self._state()
+        tag, Q = self.episode_type, len(_hip.LOG_MULTI_KEYS)
+        out = {}
+        for n, name in enumerate(self.names):
+            for q, key in enumerate(_hip.LOG_MULTI_KEYS):
+                if count[n * Q + q] > 0:
+                    out["%s/%s-%s" % (tag, name, key)] = float(value[n * Q + q])
+        out[tag + "/steps"], out[tag + "/episodes"] = counters["steps"], counters["episodes"]
+        return out
+
+    def rows(self, first=None):
+        """The rows [max(first, n_rows - capacity), n_rows) in row order: a numpy record array of ``self.row_dtype``
+        (``multi_row_dtype(A)``: the header's fields and ``agents`` [A])."""
+        n_rows = self.counters()["n_rows"]
+        lo = max(0 if first is None else int(first), n_rows - self.capacity, 0)
+        ring = self.t["rows"].cpu().numpy().view(self.row_dtype).reshape(-1)
+        return ring[np.arange(lo, max(n_rows, lo)) % self.capacity]
+
+    def records(self, level_names=None, first=None):
+        """The rows as the reference's ``log_data`` dicts (:282-302) without ``time``: lists over the agents, and the
+        ``agents`` key with their names."""
+        if level_names is None:
+            level_names = [getattr(lv, "name", None) or "level-%d" % k for k, lv in enumerate(self.pool.levels)]
+        return multi_rows_to_records(self.rows(first), level_names, self.names)
+
+    def run_summary(self, first_row=0):
+        """``summarize_run_file`` over the rows [max(first_row, n_rows - capacity), n_rows): ``success``, ``avg_length``,
+        ``reward``, ``score`` and the successful length over all rows x agents entries, ``side_effects`` over the rows;
+        ``rows`` is the number of rows, ``successes`` of successful entries."""
+        out = self.t["run_summary"]
+        _hip.check(self._lib.slhip_episode_log_run_summary_multi(self._sref, int(first_row), _hip.ptr(out),
+                                                                 _hip.current_stream_ptr()))
+        vals = out.cpu().numpy()
+        res = dict(zip(RUN_SUMMARY_FIELDS, vals.tolist()))
+        res["rows"], res["successes"] = int(vals[0]), int(vals[11])
+        return res
+
+
+def multi_rows_to_records(rows, level_names, names):
+    """``log_data`` of log_episode() for every row of a ``multi_row_dtype`` array, in the reference's key order; `names`:
+    the log's distinct agent names, which the rows' name ids index."""
+    out = []
+    for r in rows:
+        ag = r["agents"]
+        d = {"length": [int(v) for v in ag["length"]], "reward": [float(v) for v in ag["reward"]],
+             "success": [bool(v) for v in ag["success"]]}
+        if r["flags"] & _hip.LOG_JOINED:
+            d["side_effects"] = {"total": [float(r["side_effects"][0]), float(r["side_effects"][1])]}
+        d["agents"] = [names[int(v)] if int(v) < len(names) else None for v in ag["name"]]
+        d["level_name"] = level_names[int(r["level"])]
+        d["reward_possible"] = [int(v) for v in ag["reward_possible"]]
+        d["reward_needed"] = [int(v) for v in ag["reward_needed"]]
+        out.append(d)
+    return out
 
 
 def rows_to_records(rows, level_names):

@@ -39,6 +39,11 @@ class SafeLifeMultiAgentVectorEnv(object):
         from the schedule's table, an episode files one performance record -- the average over the env's agents, on the
         step where the last of them finishes -- and every agent's required points follow ``min_performance_fraction``.
         Two extra launches per step on the caller's stream, three in curriculum mode.
+    episode_log : episode_log.MultiAgentEpisodeLog (built on this pool, for num_envs envs) or None
+        the reference's ``SafeLifeLogger`` for arrays over the agents, on the device: one more launch per ``step()``, behind
+        the schedule's harvest on the same stream, files a row for every env whose agents are all done; ``episode_log.flush()``
+        joins the side-effect queue's totals in and folds the new rows into the per-name running summaries.  Needs
+        ``auto_reset=True``.  None: no launch and no allocation.
 
     ``reset()`` -> obs;  ``step(actions)`` -> (obs, reward, done, info) with
         actions  int   [B, A]   0..8 (an agent that is done takes 0: training/base_algo.py:216-219)
@@ -53,10 +58,13 @@ class SafeLifeMultiAgentVectorEnv(object):
     def __init__(self, pool, num_envs, *, time_limit=1000, remove_white_goals=True, view_shape=(15, 15),
                  output_channels=tuple(range(16)) + (25, 26, 27), auto_reset=True, first_level=None, level_stride=1,
                  env_offset=0, with_obs=True, points_on_level_exit=1, episode_streams=True, wrappers=None,
-                 side_effects=None, policy_layout=None, level_schedule=None):
+                 side_effects=None, policy_layout=None, level_schedule=None, episode_log=None):
         import torch
         if not isinstance(pool, LevelPool) or getattr(pool, "n_agents", 1) < 1:
             raise TypeError("pool must be a LevelPool")
+        if episode_log is not None and not auto_reset:      # (refused before anything is allocated)
+            raise ValueError("an episode log needs auto_reset=True: an env that stays all-done would file a row on every "
+                             "step where the reference logs the episode once")
         A = int(pool.n_agents)
         if A > _hip.SL_MAX_AGENTS:
             raise ValueError("at most %d agents per board" % _hip.SL_MAX_AGENTS)
@@ -118,6 +126,10 @@ class SafeLifeMultiAgentVectorEnv(object):
             base.struct.pool_next = level_schedule._attach(self).data_ptr()
             # (the base env's sliced and queue steppers and its rollout() refuse to run under a schedule)
             base.level_schedule = level_schedule
+        self.episode_log = episode_log
+        if episode_log is not None:         # one launch behind every step(): a row per episode whose agents are all done
+            episode_log._attach(self)
+            base.episode_log = episode_log  # (the base env's sliced and queue steppers and its rollout() refuse a log too)
 
     def _setup_extras(self, wrappers, side_effects, policy_layout):
         torch, t, base, dev = self.torch, self.t, self.base, self.device
@@ -175,6 +187,8 @@ class SafeLifeMultiAgentVectorEnv(object):
             _hip.check(self._lib.slhip_env_reset_multi(self.base._sref, self._mref, mp, _hip.current_stream_ptr()))
         if sched is not None:
             sched._rewind(mk)
+        if self.episode_log is not None:
+            self.episode_log._rewind(mk)
         if mk is not None:
             self.torch.cuda.current_stream().synchronize()      # (the mask tensor is the call's own)
         return self.obs
@@ -195,6 +209,8 @@ class SafeLifeMultiAgentVectorEnv(object):
             _hip.check(self._lib.slhip_env_step_multi(self.base._sref, self._mref, a.data_ptr(), _hip.current_stream_ptr()))
         if sched is not None:
             sched._after_step()
+        if self.episode_log is not None:
+            self.episode_log._after_step()
         self.base.steps_dispatched += 1
         return self.obs, self.reward, self.done, self.info
 
