@@ -1283,6 +1283,92 @@ int slhip_episode_log_summaries_multi(const sl_episode_log_multi *log, void *str
  * entries.  The totals go through np.nan_to_num and side_effects_frac and every score are recomputed, two passes. */
 int slhip_episode_log_run_summary_multi(const sl_episode_log_multi *log, long long first_row, double *out, void *stream);
 
+/* ---- evaluation runs: exactly N episodes, then the envs retire (additive again: five symbols and three structs, nothing
+ * existing changes; SL_ABI_VERSION stays where it is) ------------------------------------------------------------------------
+ * What the reference's trainers do with run_episodes(envs, num_episodes) (training/base_algo.py:278-318): play N episodes
+ * and stop.  No step kernel changes: small kernels on the caller's stream around the fused step read and rewrite what the
+ * step reads and writes, as the level schedule and the episode log do.
+ *
+ * The model.  A run is N TICKETS 0 .. N-1 over the pool's L slots and G envs (G: the env count over all shards; a shard
+ * holds envs g = env_offset + e, e in 0 .. B-1):
+ *     ticket t  ->  slot t % L,  env t % G,  that env's k-th episode of the run, k = t / G
+ * and the other way round env g plays tickets g, g + G, g + 2 G, ... below N.  The deal is static, so it needs no per-env
+ * successor: it is what the stride rule does with first_level = g % L and level_stride = G % L under auto_reset.  An env
+ * whose first ticket is >= N is never active.  An env that has played its last ticket RETIRES: it keeps stepping (its caller
+ * hands it action 0) and the step kernel keeps reloading it, but its output records are zeroed from the next step on, so
+ * nothing downstream -- the log's harvest, a rollout, a replay buffer, the caller -- sees these PHANTOM episodes.  The
+ * finished-episode queue still receives them (the step kernel files them): slhip_episode_run_tickets tells them apart.  A
+ * phantom episode under action 0 ends at the time limit, so a queue of N + B entries holds a whole run.
+ * The run's env must not be reset from outside between slhip_episode_run_start and the end of the run: the k of an
+ * episode is counted from base_episode. */
+typedef struct sl_episode_run_row { /* 32 bytes: one per ticket */
+    int32_t slot;                 /* t % L: the pool slot the episode was PLAYED on (scalars hold the reloaded one by then) */
+    int32_t env;                  /* t % G: the global index of the env that played it */
+    int32_t episode_idx;          /* the env's episode counter during that episode: base_episode + t / G */
+    int32_t step;                 /* the `step` argument of the harvest that filed it */
+    int32_t length;               /* info['episode']['length'] (several agents: agent 0's, as sl_episode_record) */
+    float reward;                 /* info['episode']['reward'] (agent 0's) */
+    uint8_t success, times_up;    /* (agent 0's) */
+    uint8_t flags;                /* SL_RUN_WRITTEN | SL_RUN_SCORED */
+    uint8_t reserved;
+    int32_t reserved2;
+} sl_episode_run_row;
+typedef struct sl_episode_run_agent { /* 16 bytes: one per ticket and agent */
+    int32_t length;
+    float reward;
+    uint8_t success, times_up, reserved[2];
+    int32_t reserved2;
+} sl_episode_run_agent;
+#define SL_RUN_WRITTEN 1          /* a harvest has filed the ticket */
+#define SL_RUN_SCORED 2           /* slhip_episode_run_tickets has filled side_effects[t] */
+#define SL_RUN_COUNTERS 4         /* counters[]: completed (tickets filed by this shard), in progress (active envs), env steps
+                                     taken by active envs, reserved */
+
+typedef struct sl_episode_run {   /* 80 bytes; every pointer is device memory */
+    int32_t B, G, env_offset;     /* envs of this shard, of all shards, global index of env 0 */
+    int32_t N, L;                 /* tickets, pool slots */
+    int32_t n_agents;             /* A, 1 .. SL_MAX_AGENTS */
+    uint8_t *active;              /* [B] 1 while the env has a ticket to play */
+    int32_t *played;              /* [B] episodes of the run the env has finished */
+    int32_t *base_episode;        /* [B] scalars[e].episode_idx when the run started */
+    int32_t *counters;            /* [SL_RUN_COUNTERS] */
+    sl_episode_run_row *results;  /* [N] by ticket: the content does not depend on finishing order */
+    sl_episode_run_agent *agent_results; /* [N, A] */
+    double *side_effects;         /* [N, 2] the weighted totals (agent, inaction) of slhip_episode_run_tickets */
+} sl_episode_run;
+
+/* After the reset that put env e on slot (env_offset + e) % L: base_episode[e] = scalars[e].episode_idx, played[e] = 0,
+ * active[e] = (env_offset + e < N), counters = (0, number of active envs, 0, 0), results, agent_results and side_effects all
+ * zero bytes.  One launch. */
+int slhip_episode_run_start(const sl_episode_run *run, const sl_env_scalars *scalars, void *stream);
+
+/* One launch behind every step, BEFORE the episode log's harvest.  One thread per env, grid-stride.  With g = env_offset + e:
+ *   - active[e] == 0 (retired before this step, or never active): out[e] = 16 zero bytes -- reward 0, done 0, success 0,
+ *     times_up 0, episode reward and length 0;
+ *   - active[e] != 0: the env took a step (counters[2] += 1).  If out[e].done: t = g + G * played[e]; results[t] = (t % L,
+ *     g, base_episode[e] + played[e], step, out[e].episode_length, out[e].episode_reward, out[e].success, out[e].times_up,
+ *     SL_RUN_WRITTEN); agent_results[t][0] likewise; played[e] += 1; counters[0] += 1; and if g + G * played[e] >= N the env
+ *     retires: active[e] = 0, counters[1] -= 1.  Its record of THIS step stays as the step wrote it.
+ * The counters are reduced per wave and take one integer atomicAdd per wave and counter that moved: integer sums are
+ * order-free, so the outcome is a function of the records alone.  `out` takes 16-byte records. */
+int slhip_episode_run_harvest(const sl_episode_run *run, sl_step_out *out, int step, void *stream);
+
+/* The same for records [B, A]: env e's episode ends on the step where ALL of out[e][0 .. A) have done != 0 (the step on which
+ * the multi-agent kernel reloads the env).  The row takes agent 0's length / reward / success / times_up, agent_results[t][a]
+ * every agent's; a retired env has all A records zeroed. */
+int slhip_episode_run_harvest_multi(const sl_episode_run *run, sl_step_out *out, int step, void *stream);
+
+/* Tickets of the entries of a finished-episode queue: for i < min(*count, capacity), with e = records[i].env -
+ * queue->env_base and k = records[i].episode_idx - base_episode[e],
+ *     tickets[i] = (env_offset + e) + G * k   if 0 <= e < B, k >= 0 and that is < N,   else -1
+ * (-1: an episode from before the run, or a retired env's phantom episode); tickets[i] = -1 for i >= the count.  With
+ * `scores` (and keys, n_cells, weights as slhip_episode_log_join takes them) an entry with a ticket also writes
+ * side_effects[t] = the entry's weighted totals, by the arithmetic of slhip_episode_log_join bit for bit (NaN, NaN for an
+ * entry whose keys were cut short), and sets SL_RUN_SCORED in results[t].flags.  scores == NULL: tickets only. */
+int slhip_episode_run_tickets(const sl_episode_run *run, const sl_episode_queue *queue, int32_t *tickets,
+                              const double *scores, const uint16_t *keys, const int32_t *n_cells,
+                              const sl_log_weights *weights, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

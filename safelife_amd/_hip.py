@@ -41,7 +41,10 @@ EXPORTS = (
     "slhip_episode_log_harvest", "slhip_episode_log_join", "slhip_episode_log_summaries", "slhip_episode_log_run_summary",
     "slhip_episode_log_harvest_multi", "slhip_episode_log_join_multi", "slhip_episode_log_summaries_multi",
     "slhip_episode_log_run_summary_multi",
+    "slhip_episode_run_start", "slhip_episode_run_harvest", "slhip_episode_run_harvest_multi", "slhip_episode_run_tickets",
 )
+RUN_WRITTEN, RUN_SCORED = 1, 2
+RUN_COUNTERS = ("completed", "in_progress", "env_steps", "reserved")
 LOG_JOINED, LOG_MAX_HOPS, LOG_RUN_SUMMARY = 1, 64, 12
 LOG_MAX_NAMES, LOG_NO_NAME = 16, 0xFF
 #: the per-name summaries' keys of a multi-agent log, in the reference's order
@@ -225,6 +228,13 @@ class EpisodeLogMulti(C.Structure):
                                              "reward_possible", "name_id", "value", "count", "weight")])
 
 
+class EpisodeRun(C.Structure):
+    """struct sl_episode_run (80 bytes)"""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "G", "env_offset", "N", "L", "n_agents")]
+                + [(n, C.c_void_p) for n in ("active", "played", "base_episode", "counters", "results", "agent_results",
+                                             "side_effects")])
+
+
 def log_row_multi_bytes(n_agents):
     """SL_LOG_ROW_MULTI_BYTES(A): a 64-byte header and 40 bytes per agent."""
     return 64 + 40 * int(n_agents)
@@ -363,6 +373,11 @@ def lib():
                                                    C.POINTER(LogWeights), _p]
         L.slhip_episode_log_summaries_multi.argtypes = [C.POINTER(EpisodeLogMulti), _p]
         L.slhip_episode_log_run_summary_multi.argtypes = [C.POINTER(EpisodeLogMulti), C.c_longlong, _p, _p]
+        L.slhip_episode_run_start.argtypes = [C.POINTER(EpisodeRun), _p, _p]
+        L.slhip_episode_run_harvest.argtypes = [C.POINTER(EpisodeRun), _p, C.c_int, _p]
+        L.slhip_episode_run_harvest_multi.argtypes = [C.POINTER(EpisodeRun), _p, C.c_int, _p]
+        L.slhip_episode_run_tickets.argtypes = [C.POINTER(EpisodeRun), C.POINTER(EpisodeQueue), _p, _p, _p, _p,
+                                                C.POINTER(LogWeights), _p]
         L.slhip_obs_to_policy.argtypes = [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]
         L.slhip_gather_unique_id.argtypes = [_p]
         L.slhip_gather_init.argtypes = [_p, C.c_int, C.c_int, C.POINTER(_p)]

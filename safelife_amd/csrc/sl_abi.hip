@@ -2061,4 +2061,60 @@ int slhip_episode_log_run_summary_multi(const sl_episode_log_multi *log, long lo
     return err == hipSuccess ? SL_OK : hip_fail(err, "episode_log_run_summary_multi launch");
 }
 
+// ---- evaluation runs (sl_episode_run.hip)
+
+static int check_episode_run(const sl_episode_run *run, const char *who) {
+    if (!run) return fail(SL_E_ARG, std::string(who) + ": null run description");
+    if (run->B < 1 || run->L < 1 || run->N < 1) return fail(SL_E_SHAPE, std::string(who) + ": B, L and N must be at least 1");
+    if (run->env_offset < 0 || run->G < run->B || run->env_offset > run->G - run->B)
+        return fail(SL_E_SHAPE, std::string(who) + ": the shard's envs env_offset .. env_offset + B - 1 must lie in 0 .. G-1");
+    if (run->n_agents < 1 || run->n_agents > SL_MAX_AGENTS)
+        return fail(SL_E_SHAPE, std::string(who) + ": n_agents outside 1..SL_MAX_AGENTS");
+    if (!run->active || !run->played || !run->base_episode || !run->counters || !run->results || !run->agent_results ||
+        !run->side_effects)
+        return fail(SL_E_ARG, std::string(who) + ": null pointer in the run description");
+    return SL_OK;
+}
+
+int slhip_episode_run_start(const sl_episode_run *run, const sl_env_scalars *scalars, void *stream) {
+    if (int rc = check_episode_run(run, "episode_run_start")) return rc;
+    if (!scalars) return fail(SL_E_ARG, "episode_run_start: null scalars");
+    const hipError_t err = sl::launch_episode_run_start(*run, scalars, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "episode_run_start launch");
+}
+
+int slhip_episode_run_harvest(const sl_episode_run *run, sl_step_out *out, int step, void *stream) {
+    if (int rc = check_episode_run(run, "episode_run_harvest")) return rc;
+    if (run->n_agents != 1) return fail(SL_E_SHAPE, "episode_run_harvest: records [B] are a single-agent env's (see _multi)");
+    if (!out) return fail(SL_E_ARG, "episode_run_harvest: null out");
+    const hipError_t err = sl::launch_episode_run_harvest(*run, out, step, false, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "episode_run_harvest launch");
+}
+
+int slhip_episode_run_harvest_multi(const sl_episode_run *run, sl_step_out *out, int step, void *stream) {
+    if (int rc = check_episode_run(run, "episode_run_harvest_multi")) return rc;
+    if (!out) return fail(SL_E_ARG, "episode_run_harvest_multi: null out");
+    const hipError_t err = sl::launch_episode_run_harvest(*run, out, step, true, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "episode_run_harvest_multi launch");
+}
+
+int slhip_episode_run_tickets(const sl_episode_run *run, const sl_episode_queue *queue, int32_t *tickets,
+                              const double *scores, const uint16_t *keys, const int32_t *n_cells,
+                              const sl_log_weights *weights, void *stream) {
+    if (int rc = check_episode_run(run, "episode_run_tickets")) return rc;
+    if (!queue || !tickets) return fail(SL_E_ARG, "episode_run_tickets: null queue / tickets");
+    if (queue->capacity < 1) return fail(SL_E_SHAPE, "episode_run_tickets: the queue has no slots");
+    if (!queue->count || !queue->records) return fail(SL_E_ARG, "episode_run_tickets: null count / records");
+    sl_log_weights none;
+    memset(&none, 0, sizeof(none));
+    if (scores) {
+        if (!keys || !n_cells || !weights) return fail(SL_E_ARG, "episode_run_tickets: scores without keys / n_cells / weights");
+        if (weights->n < 0 || weights->n > SL_SE_MAX_KEYS)
+            return fail(SL_E_SHAPE, "episode_run_tickets: weights.n outside 0..SL_SE_MAX_KEYS");
+    }
+    const hipError_t err = sl::launch_episode_run_tickets(*run, *queue, tickets, scores, keys, n_cells,
+                                                          scores ? *weights : none, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "episode_run_tickets launch");
+}
+
 }  // extern "C"

@@ -146,6 +146,12 @@ hipError_t launch_episode_log_join_multi(const sl_episode_log_multi &log, const 
 hipError_t launch_episode_log_summaries_multi(const sl_episode_log_multi &log, hipStream_t stream);
 hipError_t launch_episode_log_run_summary_multi(const sl_episode_log_multi &log, long long first_row, double *out,
                                                 hipStream_t stream);
+// evaluation runs (sl_episode_run.hip): N tickets dealt statically, retired envs masked, tickets of queue entries
+hipError_t launch_episode_run_start(const sl_episode_run &run, const sl_env_scalars *scalars, hipStream_t stream);
+hipError_t launch_episode_run_harvest(const sl_episode_run &run, sl_step_out *out, int step, bool multi, hipStream_t stream);
+hipError_t launch_episode_run_tickets(const sl_episode_run &run, const sl_episode_queue &queue, int32_t *tickets,
+                                      const double *scores, const uint16_t *keys, const int32_t *n_cells,
+                                      const sl_log_weights &weights, hipStream_t stream);
 // envs [e_first, e_first + e_count) of the batch; actions / reward_t / done_t are indexed [t * tstride + e]
 // with the env's index in the whole batch
 // (sl_aql.hip dispatches the same kernel from queues of the library's own: PreparedStep below)

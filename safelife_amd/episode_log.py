@@ -191,6 +191,14 @@ class EpisodeLog(object):
         self.summarise()
         return batch
 
+    def reset_summary(self):
+        """``SafeLifeLogger.reset_summary()`` (safelife_logger.py:406-414): the running summaries start over --
+        ``summary_stats``, ``summary_counts`` and the weights the next values meet go to zero, on the caller's stream.  Rows
+        and counters stay; rows not yet summarised are still folded in by the next ``flush()``."""
+        if self.t is None:
+            raise ValueError("the episode log has no device state yet: hand it to SafeLifeVectorEnv(episode_log=...)")
+        self.t["state"][5:].zero_()
+
     # ---- host side: each of these is one visit
 
     def _state(self):
@@ -406,6 +414,14 @@ class MultiAgentEpisodeLog(object):
             self.join(batch.count, batch.rec_tensor, emd["scores"], batch.keys, emd["n_cells"])
         self.summarise()
         return batch
+
+    def reset_summary(self):
+        """``SafeLifeLogger.reset_summary()``, as ``EpisodeLog.reset_summary``: every name's summaries start over; rows and
+        counters stay."""
+        if self.t is None:
+            raise ValueError("the episode log has no device state yet: hand it to "
+                             "SafeLifeMultiAgentVectorEnv(episode_log=...)")
+        self.t["state"][5:].zero_()
 
     # ---- host side: each of these is one visit
 

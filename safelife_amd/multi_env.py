@@ -44,6 +44,11 @@ class SafeLifeMultiAgentVectorEnv(object):
         the schedule's harvest on the same stream, files a row for every env whose agents are all done; ``episode_log.flush()``
         joins the side-effect queue's totals in and folds the new rows into the per-name running summaries.  Needs
         ``auto_reset=True``.  None: no launch and no allocation.
+    episode_run : episode_run.EpisodeRun (built on this pool with ``n_agents=A``) or None
+        a bounded evaluation run, the reference's ``run_episodes(envs, num_episodes)``: build the env with
+        ``**run.env_arguments()``; after ``run.start()`` one more launch per ``step()``, in front of the log's harvest, files
+        the episodes whose agents are all done by ticket, retires the envs that have no ticket left and zeroes every
+        record of a retired env.  Refuses ``level_schedule`` and ``wrappers``.  None: no launch and no allocation.
 
     ``reset()`` -> obs;  ``step(actions)`` -> (obs, reward, done, info) with
         actions  int   [B, A]   0..8 (an agent that is done takes 0: training/base_algo.py:216-219)
@@ -58,7 +63,7 @@ class SafeLifeMultiAgentVectorEnv(object):
     def __init__(self, pool, num_envs, *, time_limit=1000, remove_white_goals=True, view_shape=(15, 15),
                  output_channels=tuple(range(16)) + (25, 26, 27), auto_reset=True, first_level=None, level_stride=1,
                  env_offset=0, with_obs=True, points_on_level_exit=1, episode_streams=True, wrappers=None,
-                 side_effects=None, policy_layout=None, level_schedule=None, episode_log=None):
+                 side_effects=None, policy_layout=None, level_schedule=None, episode_log=None, episode_run=None):
         import torch
         if not isinstance(pool, LevelPool) or getattr(pool, "n_agents", 1) < 1:
             raise TypeError("pool must be a LevelPool")
@@ -68,6 +73,9 @@ class SafeLifeMultiAgentVectorEnv(object):
         A = int(pool.n_agents)
         if A > _hip.SL_MAX_AGENTS:
             raise ValueError("at most %d agents per board" % _hip.SL_MAX_AGENTS)
+        if episode_run is not None:         # (refused before anything is allocated)
+            episode_run._check_env(pool, num_envs, A, auto_reset, first_level, level_stride, env_offset, level_schedule,
+                                   wrappers)
         if level_schedule is not None:
             level_schedule._check_env(pool, A)
             if first_level is None:
@@ -130,6 +138,10 @@ class SafeLifeMultiAgentVectorEnv(object):
         if episode_log is not None:         # one launch behind every step(): a row per episode whose agents are all done
             episode_log._attach(self)
             base.episode_log = episode_log  # (the base env's sliced and queue steppers and its rollout() refuse a log too)
+        self.episode_run = episode_run
+        if episode_run is not None:         # one launch behind every step() of a started run, in front of the log's
+            episode_run._attach(self)
+            base.episode_run = episode_run  # (... and a run)
 
     def _setup_extras(self, wrappers, side_effects, policy_layout):
         torch, t, base, dev = self.torch, self.t, self.base, self.device
@@ -209,6 +221,8 @@ class SafeLifeMultiAgentVectorEnv(object):
             _hip.check(self._lib.slhip_env_step_multi(self.base._sref, self._mref, a.data_ptr(), _hip.current_stream_ptr()))
         if sched is not None:
             sched._after_step()
+        if self.episode_run is not None:
+            self.episode_run._after_step()
         if self.episode_log is not None:
             self.episode_log._after_step()
         self.base.steps_dispatched += 1

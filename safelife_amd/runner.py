@@ -22,6 +22,9 @@ the env's facts and holds every piece of a step that they share (first reset, mo
 returned, device draw, env step).  A runner puts the pieces in its order and adds what is its own: its draw, what its
 step result is made of, and ``gen_training_batch`` or ``collect``.  The two multi-agent runners keep who is active in an
 ``_AgentState`` each.  ``PipelinedRunner`` is another loop (groups of envs on streams of their own).
+
+``run_episodes`` of the shared loop is the reference's evaluation (training/base_algo.py:278-318): exactly N episodes over
+the env's ``episode_run.EpisodeRun``, every runner stepping with its own ``take_one_step``.
 """
 import collections
 
@@ -130,6 +133,53 @@ class _Runner(object):
         self.env.step(actions)
         return self._reward().clone(), self.env.done.to(self.torch.bool)
 
+    def _live_run(self):
+        """The env's ``EpisodeRun`` while a run is on (started), else None."""
+        run = getattr(self.env, "episode_run", None)
+        return run if (run is not None and run._live) else None
+
+    def _mask_retired(self, actions):
+        """Retired envs of a live run get action 0 (in place; ``actions`` integers ``[B]``)."""
+        run = self._live_run()
+        if run is not None:
+            actions.mul_(run.active)
+        return actions
+
+    def _run_begins(self):
+        """What a runner carries from step to step starts over with the run's reset."""
+
+    def run_episodes(self, num_episodes=None, poll_every=16, **how):
+        """The reference's ``run_episodes`` (training/base_algo.py:278-318) over the env's ``EpisodeRun``: the log's
+        ``reset_summary()`` if the env has a log, ``run.start()``, steps until every ticket has been played -- the run's
+        counter is read once every ``poll_every`` steps; the steps past the end are harmless, every env is retired and masked
+        by then -- and the log's ``flush()``, which is what ``log_summary`` reports.  Retired envs get action 0.
+        ``num_episodes`` is the run's (None: that); ``num_steps`` is not advanced, as the reference's trainers do not count
+        test steps.  Returns ``run.results()``, rows by ticket."""
+        run = getattr(self.env, "episode_run", None)
+        if run is None:
+            raise ValueError("run_episodes() needs an env built with episode_run=EpisodeRun(...)")
+        if num_episodes is not None and int(num_episodes) != run.num_episodes:
+            raise ValueError("the env's EpisodeRun was built for %d episodes, not %d: its result table is sized by that"
+                             % (run.num_episodes, int(num_episodes)))
+        poll_every = max(1, int(poll_every))
+        log = getattr(self.env, "episode_log", None)
+        if log is not None:
+            log.reset_summary()
+        num_steps = self.num_steps
+        run.start()
+        self._started = True
+        self._run_begins()
+        steps = 0
+        while True:
+            self.take_one_step(**how)
+            steps += 1
+            if steps % poll_every == 0 and run.finished():
+                break
+        self.num_steps = num_steps
+        if log is not None:
+            log.flush()
+        return run.results()
+
 
 class _ReplayCollector(object):
     """``collect`` of the two DQN runners."""
@@ -191,6 +241,7 @@ class VectorRunner(_Runner):
         obs, agent_ids = self.obs_for_envs()
         values, policies = self._call(self.policy, obs)
         actions = self.torch.multinomial(policies, 1, generator=self.generator).squeeze(1)
+        self._mask_retired(actions)
         kept = obs.clone() if self.copy_obs else obs
         next_obs, rewards, done = self.act_on_envs(actions)
         return StepResult(kept, actions, rewards, done, next_obs, agent_ids, policies, values)
@@ -261,6 +312,7 @@ class DQNRunner(_ReplayCollector, _Runner):
         agent_ids = (self.env_ids, self.num_resets.clone())
         qvals = self._draw_input(self._call(self.q_model, obs))
         self._draw(self._lib.slhip_sample_actions_eps, _hip.ptr(qvals), self._rows, qvals.shape[1], float(epsilon))
+        self._mask_retired(self.actions)
         kept = obs.clone()
         rewards, done = self._env_step(self.actions)
         self.num_resets += done.to(self.torch.int64)
@@ -415,9 +467,16 @@ class _MultiAgentRunner(_Runner):
     def _agent_rows(self, obs):
         return obs.view((self._rows,) + tuple(obs.shape[2:]))
 
+    def _run_begins(self):
+        self._state.active.fill_(1)         # (every env has just been reset)
+
     def _masked_step(self, obs, x, entry, *epsilon):
         """From the model's checked output ``x`` on: the masked draw, the fused step, the agent-step count -- everything
-        but moving the state on.  -> ``obs actions rewards done next_obs agent_ids active``, the first two own copies."""
+        but moving the state on.  -> ``obs actions rewards done next_obs agent_ids active``, the first two own copies.
+        The agents of an env that a live ``EpisodeRun`` has retired are inactive: action 0, no rollout or replay row."""
+        run = self._live_run()
+        if run is not None:
+            self._state.active.mul_(run.active[:, None])
         active = self._state.active.clone()
         agent_ids = (self.env_ids, self._state.num_resets.clone())
         self._draw(entry, _hip.ptr(x), _hip.ptr(active), self._rows, x.shape[1], *epsilon)

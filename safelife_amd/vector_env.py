@@ -299,18 +299,28 @@ class SafeLifeVectorEnv(object):
                                    episode; ``episode_log.flush()`` joins the side-effect queue's totals in and folds the
                                    rows into the running summaries.  Only ``step()`` and ``reset()`` drive a log, as with a
                                    schedule.  None: nothing changes -- no launch, no allocation.
+    episode_run : episode_run.EpisodeRun or None
+                                   a bounded evaluation run, the reference's ``run_episodes(envs, num_episodes)``: build the
+                                   env with ``**run.env_arguments()``; after ``run.start()`` one kernel behind every
+                                   ``step()`` (in front of the log's harvest, on the same stream) files the episodes that
+                                   ended by ticket, retires the envs that have none left and zeroes retired envs' records.
+                                   Refuses ``level_schedule``, a refreshable pool, ``wrappers`` and the sliced and queue
+                                   steppers.  None: nothing changes -- no launch, no allocation.
     """
 
     def __init__(self, pool, num_envs, *, time_limit=1000, remove_white_goals=True,
                  view_shape=(15, 15), output_channels=_DEFAULT_CHANNELS, auto_reset=True,
                  first_level=None, level_stride=1, env_offset=0, with_obs=True,
                  points_on_level_exit=1, wrappers=None, slices=1, episode_streams=True, side_effects=None,
-                 policy_layout=None, level_schedule=None, episode_log=None):
+                 policy_layout=None, level_schedule=None, episode_log=None, episode_run=None):
         import torch
         self.torch = torch
         if not isinstance(pool, LevelPool):
             raise TypeError("pool must be a LevelPool")
         self.pool = pool
+        if episode_run is not None:         # (refused before anything is allocated)
+            episode_run._check_env(pool, num_envs, 1, auto_reset, first_level, level_stride, env_offset, level_schedule,
+                                   wrappers)
         if level_schedule is not None and level_schedule.n_agents > 1:      # (refused before anything is allocated)
             level_schedule._check_env(pool, None)
         self.device = _hip.device()
@@ -430,6 +440,9 @@ class SafeLifeVectorEnv(object):
         self.episode_log = episode_log
         if episode_log is not None:         # one launch behind every step(): a row per finished episode
             episode_log._attach(self)
+        self.episode_run = episode_run
+        if episode_run is not None:         # one launch behind every step() of a started run, in front of the log's
+            episode_run._attach(self)
         self._lib = _hip.lib()
         self._sref = C.byref(s)
         # slices: boundaries at multiples of 64 envs (keeps every slice 16-byte aligned for the row kernels)
@@ -777,6 +790,9 @@ class SafeLifeVectorEnv(object):
             raise ValueError("%s cannot drive a level schedule: %s (use step())" % (what, why))
         if self.episode_log is not None:
             raise ValueError("%s cannot drive an episode log: %s (use step())" % (what, log_why))
+        run = getattr(self, "episode_run", None)
+        if run is not None:
+            raise ValueError("%s cannot drive an episode run: %s (use step())" % (what, run.STEPPERS))
 
     def _actions(self, actions, shape):
         torch = self.torch
@@ -802,6 +818,8 @@ class SafeLifeVectorEnv(object):
         _hip.check(rc)
         if sched is not None:
             sched._after_step()
+        if self.episode_run is not None:
+            self.episode_run._after_step()
         if self.episode_log is not None:
             self.episode_log._after_step()
         self._caller_ahead = True
