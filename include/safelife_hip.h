@@ -1369,6 +1369,105 @@ int slhip_episode_run_tickets(const sl_episode_run *run, const sl_episode_queue 
                               const double *scores, const uint16_t *keys, const int32_t *n_cells,
                               const sl_log_weights *weights, void *stream);
 
+/* ---- episode histories: the board frames of selected episodes (additive again: two symbols and two structs, nothing existing
+ * changes; SL_ABI_VERSION stays where it is) --------------------------------------------------------------------------------
+ * What the reference's SafeLifeLogWrapper records (safelife_logger.py:560-592: game.board and game.goals appended after every
+ * step) and SafeLifeLogger.log_episode keeps when (num_episodes - 1) % video_interval == 0 (:338-347).  No step kernel
+ * changes: a recorder behind every step copies the boards of a small, fixed set of WATCHED envs into frame slots, and the
+ * reference's interval rule decides at the episode's end which slots are kept.
+ *
+ * The model.
+ *   watch       n ascending, distinct env indices in 0 .. B-1 (n <= SL_HIST_MAX_WATCH).
+ *   slots       K <= SL_HIST_MAX_SLOTS; slot s holds one goals plane goals[s] uint16 [H,W] and T = time_limit board frames
+ *               frames[s] uint16 [T,H,W].  slot_state[s]: SL_HIST_SLOT_FREE, _ENV (owned by the watched env i with
+ *               owner[i] == s) or _ENTRY (held by the history entries[s]).
+ *   owner[i]    the slot watched env i records into, or -1.  An env acquires a slot only where an episode STARTS -- a rewind
+ *               (attach, a reset that reloads it) or the capture of the step that ended its previous episode -- never in
+ *               mid-episode, so no history is partial at the front.
+ *   free order  the envs that need a slot in one call take the free slots in ascending order on both sides: the r-th such
+ *               env (ascending env index) takes the r-th free slot (ascending slot index) as slot_state stood when the call
+ *               began; an env beyond the last free slot owns none (-1) until a later episode start finds one.
+ *   an episode's start (for env e = watch[i]): cur_level[i] = scalars[e].level_idx, cur_episode[i] = scalars[e].episode_idx
+ *               (after an in-kernel reload scalars[e] describes the NEXT episode, which is why these are kept), and, if the
+ *               env owns a slot s, goals[s] = goals[e] as the reload left it.  A slot keeps ONE goals plane: histories are for
+ *               pools whose goals are static (safelife_game.py:753-760).
+ *
+ * slhip_history_capture, behind every step.  `active` (may be NULL) is a mask uint8 [B]: an env with active[e] == 0 is
+ * neither captured nor counted (an evaluation run's retired envs and their phantom episodes).  With done(e) = out[e].done != 0
+ * and the env not masked out:
+ *   numbering   the episodes that end in this call are numbered counters[0] + rank(e), rank(e) = the number of done envs below
+ *               e over ALL B envs: the episode log's row index, the reference's num_episodes - 1.  A function of the done
+ *               flags alone.  counters[0] += the number of done envs.
+ *   the queue   only entries [counters[4], min(*queue.count, queue.capacity)) are looked at (counters[4], the cursor, then
+ *               moves to that end; whoever installs a fresh queue zeroes it).  final(i) = the smallest such j with
+ *               records[j].env - env_base == watch[i] and records[j].episode_idx == cur_episode[i], or none.
+ *   per watched env i, e = watch[i], not masked out, s = owner[i]:
+ *     not done, s >= 0:  frames[s][scalars[e].episode_length - 1] = board[e]
+ *     done, number % interval == 0 (KEPT by rule):
+ *        s < 0:   counters[2] (missed) += 1
+ *        s >= 0:  counters[1] (kept) += 1; entries[s] = (row = number, e, cur_level[i], cur_episode[i], length =
+ *                 out[e].episode_length, s, out[e].success, out[e].times_up, flags); slot_state[s] = SL_HIST_SLOT_ENTRY;
+ *                 the env owns no slot any more.  With final(i) = j: frames[s][length - 1] = queue.boards[j], the board as the
+ *                 agent left it, flags = SL_HIST_LIVE.  Without (the queue overflowed): the history lacks its last frame,
+ *                 flags = SL_HIST_LIVE | SL_HIST_NO_FINAL, counters[3] (incomplete) += 1.
+ *     done, not kept:    the slot stays with the env; the next episode overwrites it from frame 0.
+ *     done (either way): an episode starts, as above; an env without a slot takes one by the free order.
+ *   A frame index outside 0 .. T-1 is not written.  The entries of one call, sorted by row, are in ascending env order.
+ *
+ * Two launches: a bookkeeping pass in ONE workgroup (the done scan of slhip_episode_log_harvest, the new queue entries walked
+ * through LDS by the lanes of the watched envs whose episode ended, two more workgroup scans for the free order) leaves one copy order per watched env in orders[i] (8 int32: source 0 none / 1 live board
+ * / 2 queue board, queue index, slot, frame, the slot whose goals plane takes goals[e] or -1, 3 reserved); a copy pass over
+ * watched envs x {frame, goals plane} carries them out with vector loads and stores of the widest of 16 / 8 / 4 / 2 bytes that
+ * divides both addresses (a 25x25 board is 1250 bytes: odd envs are 2-byte aligned), and 2-byte ones for the rest.  No global
+ * atomics. */
+#define SL_HIST_LIVE 1            /* entries[s].flags: the entry holds slot s */
+#define SL_HIST_NO_FINAL 2        /* the final frame (index length - 1) was not in the queue */
+#define SL_HIST_SLOT_FREE 0
+#define SL_HIST_SLOT_ENV 1
+#define SL_HIST_SLOT_ENTRY 2
+#define SL_HIST_MAX_WATCH 1024
+#define SL_HIST_MAX_SLOTS 1024
+#define SL_HIST_COUNTERS 8        /* counters[]: episodes, kept, missed, incomplete, cursor, 3 reserved */
+#define SL_HIST_ORDER_WORDS 8
+typedef struct sl_history_entry { /* 32 bytes */
+    int64_t row;                  /* the episode's number: the episode log's row index */
+    int32_t env, level, episode_idx; /* the level slot PLAYED and the env's episode counter during the episode */
+    int32_t length;               /* info['episode']['length']: frames 0 .. length - 1 (length - 2 with SL_HIST_NO_FINAL) */
+    int32_t slot;
+    uint8_t success, times_up;
+    uint8_t flags;                /* SL_HIST_LIVE | SL_HIST_NO_FINAL; 0: released */
+    uint8_t reserved;
+} sl_history_entry;
+
+typedef struct sl_episode_history { /* 112 bytes; every pointer is device memory */
+    int32_t B, n_watch, n_slots;  /* envs, watched envs n, slots K */
+    int32_t T, H, W;              /* frames per slot (the env's time_limit) and the board shape */
+    int32_t interval;             /* >= 1 */
+    int32_t reserved;
+    const int32_t *watch;         /* [n] */
+    int32_t *owner;               /* [n] */
+    int32_t *cur_level;           /* [n] */
+    int32_t *cur_episode;         /* [n] */
+    int32_t *slot_state;          /* [K] */
+    sl_history_entry *entries;    /* [K]: entries[s] is the history held in slot s */
+    long long *counters;          /* [SL_HIST_COUNTERS] */
+    uint16_t *goals;              /* [K,H,W] */
+    uint16_t *frames;             /* [K,T,H,W] */
+    int32_t *orders;              /* [n, SL_HIST_ORDER_WORDS]: workspace between the two launches; 16-byte aligned */
+} sl_episode_history;
+
+/* board, goals uint16 [B,H,W]; scalars [B] and out [B] as the step left them; queue: the env's finished-episode queue
+ * (capacity 0: none -- every kept history then lacks its final frame). */
+int slhip_history_capture(const sl_episode_history *hist, const uint16_t *board, const uint16_t *goals,
+                          const sl_env_scalars *scalars, const sl_step_out *out, const sl_episode_queue *queue,
+                          const uint8_t *active, void *stream);
+
+/* After the envs with mask[e] != 0 (mask == NULL: all) have been reloaded from outside the step, and once at attach: for
+ * every such watched env an episode starts, as above -- it keeps the slot it owns and restarts at frame 0 on its new level, or
+ * takes one by the free order.  Counters and entries are not touched.  The same two launches. */
+int slhip_history_rewind(const sl_episode_history *hist, const uint16_t *goals, const sl_env_scalars *scalars,
+                         const uint8_t *mask, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,7 +42,12 @@ EXPORTS = (
     "slhip_episode_log_harvest_multi", "slhip_episode_log_join_multi", "slhip_episode_log_summaries_multi",
     "slhip_episode_log_run_summary_multi",
     "slhip_episode_run_start", "slhip_episode_run_harvest", "slhip_episode_run_harvest_multi", "slhip_episode_run_tickets",
+    "slhip_history_capture", "slhip_history_rewind",
 )
+HIST_LIVE, HIST_NO_FINAL = 1, 2
+HIST_SLOT_FREE, HIST_SLOT_ENV, HIST_SLOT_ENTRY = 0, 1, 2
+HIST_MAX_WATCH, HIST_MAX_SLOTS, HIST_ORDER_WORDS = 1024, 1024, 8
+HIST_COUNTERS = ("episodes", "kept", "missed", "incomplete", "cursor", "reserved0", "reserved1", "reserved2")
 RUN_WRITTEN, RUN_SCORED = 1, 2
 RUN_COUNTERS = ("completed", "in_progress", "env_steps", "reserved")
 LOG_JOINED, LOG_MAX_HOPS, LOG_RUN_SUMMARY = 1, 64, 12
@@ -228,6 +233,13 @@ class EpisodeLogMulti(C.Structure):
                                              "reward_possible", "name_id", "value", "count", "weight")])
 
 
+class EpisodeHistory(C.Structure):
+    """struct sl_episode_history (112 bytes)"""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "n_watch", "n_slots", "T", "H", "W", "interval", "reserved")]
+                + [(n, C.c_void_p) for n in ("watch", "owner", "cur_level", "cur_episode", "slot_state",
+                                             "entries", "counters", "goals", "frames", "orders")])
+
+
 class EpisodeRun(C.Structure):
     """struct sl_episode_run (80 bytes)"""
     _fields_ = ([(n, C.c_int32) for n in ("B", "G", "env_offset", "N", "L", "n_agents")]
@@ -378,6 +390,8 @@ def lib():
         L.slhip_episode_run_harvest_multi.argtypes = [C.POINTER(EpisodeRun), _p, C.c_int, _p]
         L.slhip_episode_run_tickets.argtypes = [C.POINTER(EpisodeRun), C.POINTER(EpisodeQueue), _p, _p, _p, _p,
                                                 C.POINTER(LogWeights), _p]
+        L.slhip_history_capture.argtypes = [C.POINTER(EpisodeHistory), _p, _p, _p, _p, C.POINTER(EpisodeQueue), _p, _p]
+        L.slhip_history_rewind.argtypes = [C.POINTER(EpisodeHistory), _p, _p, _p, _p]
         L.slhip_obs_to_policy.argtypes = [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]
         L.slhip_gather_unique_id.argtypes = [_p]
         L.slhip_gather_init.argtypes = [_p, C.c_int, C.c_int, C.POINTER(_p)]

@@ -2117,4 +2117,45 @@ int slhip_episode_run_tickets(const sl_episode_run *run, const sl_episode_queue 
     return err == hipSuccess ? SL_OK : hip_fail(err, "episode_run_tickets launch");
 }
 
+// ---- episode histories (sl_history.hip)
+
+static int check_history(const sl_episode_history *h, const char *who) {
+    if (!h) return fail(SL_E_ARG, std::string(who) + ": null history description");
+    if (h->B < 1 || h->n_watch < 1 || h->n_watch > h->B || h->n_watch > SL_HIST_MAX_WATCH)
+        return fail(SL_E_SHAPE, std::string(who) + ": 1 <= n_watch <= min(B, SL_HIST_MAX_WATCH) does not hold");
+    if (h->n_slots < 1 || h->n_slots > SL_HIST_MAX_SLOTS)
+        return fail(SL_E_SHAPE, std::string(who) + ": n_slots outside 1..SL_HIST_MAX_SLOTS");
+    if (h->T < 1 || h->interval < 1) return fail(SL_E_SHAPE, std::string(who) + ": T and interval must be at least 1");
+    if (h->H < 3 || h->W < 3 || (long long)h->H * h->W > SL_MAX_CELLS)
+        return fail(SL_E_SHAPE, std::string(who) + ": boards are at least 3x3 and at most SL_MAX_CELLS cells");
+    if (!h->watch || !h->owner || !h->cur_level || !h->cur_episode || !h->slot_state || !h->entries ||
+        !h->counters || !h->goals || !h->frames || !h->orders)
+        return fail(SL_E_ARG, std::string(who) + ": null array");
+    return SL_OK;
+}
+
+int slhip_history_capture(const sl_episode_history *hist, const uint16_t *board, const uint16_t *goals,
+                          const sl_env_scalars *scalars, const sl_step_out *out, const sl_episode_queue *queue,
+                          const uint8_t *active, void *stream) {
+    if (int rc = check_history(hist, "history_capture")) return rc;
+    if (!board || !goals || !scalars || !out) return fail(SL_E_ARG, "history_capture: null board / goals / scalars / out");
+    sl_episode_queue q;
+    memset(&q, 0, sizeof(q));
+    if (queue && queue->capacity > 0) {
+        if (!queue->count || !queue->records || !queue->boards)
+            return fail(SL_E_ARG, "history_capture: a queue with slots needs count, records and boards");
+        q = *queue;
+    }
+    const hipError_t err = sl::launch_history_capture(*hist, board, goals, scalars, out, q, active, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "history_capture launch");
+}
+
+int slhip_history_rewind(const sl_episode_history *hist, const uint16_t *goals, const sl_env_scalars *scalars,
+                         const uint8_t *mask, void *stream) {
+    if (int rc = check_history(hist, "history_rewind")) return rc;
+    if (!goals || !scalars) return fail(SL_E_ARG, "history_rewind: null goals / scalars");
+    const hipError_t err = sl::launch_history_rewind(*hist, goals, scalars, mask, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "history_rewind launch");
+}
+
 }  // extern "C"

@@ -152,6 +152,12 @@ hipError_t launch_episode_run_harvest(const sl_episode_run &run, sl_step_out *ou
 hipError_t launch_episode_run_tickets(const sl_episode_run &run, const sl_episode_queue &queue, int32_t *tickets,
                                       const double *scores, const uint16_t *keys, const int32_t *n_cells,
                                       const sl_log_weights &weights, hipStream_t stream);
+// episode histories (sl_history.hip): the board frames of selected episodes of the watched envs; two launches each
+hipError_t launch_history_capture(const sl_episode_history &h, const uint16_t *board, const uint16_t *goals,
+                                  const sl_env_scalars *scalars, const sl_step_out *out, const sl_episode_queue &queue,
+                                  const uint8_t *active, hipStream_t stream);
+hipError_t launch_history_rewind(const sl_episode_history &h, const uint16_t *goals, const sl_env_scalars *scalars,
+                                 const uint8_t *mask, hipStream_t stream);
 // envs [e_first, e_first + e_count) of the batch; actions / reward_t / done_t are indexed [t * tstride + e]
 // with the env's index in the whole batch
 // (sl_aql.hip dispatches the same kernel from queues of the library's own: PreparedStep below)

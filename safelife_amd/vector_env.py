@@ -306,13 +306,20 @@ class SafeLifeVectorEnv(object):
                                    ended by ticket, retires the envs that have none left and zeroes retired envs' records.
                                    Refuses ``level_schedule``, a refreshable pool, ``wrappers`` and the sliced and queue
                                    steppers.  None: nothing changes -- no launch, no allocation.
+    episode_history : episode_history.EpisodeHistory or None
+                                   the board frames of selected episodes, the reference's ``SafeLifeLogWrapper`` history and
+                                   ``video_interval`` rule: two small launches behind every ``step()`` (in front of the run's
+                                   and the log's harvests, on the same stream) copy the watched envs' boards into frame slots
+                                   and keep every ``interval``-th episode's.  Needs ``side_effects=`` (an episode's last frame
+                                   comes from the finished-episode queue) and static goals; refuses a refreshable pool and the
+                                   sliced and queue steppers.  None: nothing changes -- no launch, no allocation.
     """
 
     def __init__(self, pool, num_envs, *, time_limit=1000, remove_white_goals=True,
                  view_shape=(15, 15), output_channels=_DEFAULT_CHANNELS, auto_reset=True,
                  first_level=None, level_stride=1, env_offset=0, with_obs=True,
                  points_on_level_exit=1, wrappers=None, slices=1, episode_streams=True, side_effects=None,
-                 policy_layout=None, level_schedule=None, episode_log=None, episode_run=None):
+                 policy_layout=None, level_schedule=None, episode_log=None, episode_run=None, episode_history=None):
         import torch
         self.torch = torch
         if not isinstance(pool, LevelPool):
@@ -324,6 +331,8 @@ class SafeLifeVectorEnv(object):
         if level_schedule is not None and level_schedule.n_agents > 1:      # (refused before anything is allocated)
             level_schedule._check_env(pool, None)
         self.device = _hip.device()
+        if episode_history is not None:     # (refused before anything is allocated)
+            episode_history._check_env(pool, num_envs, time_limit, side_effects, torch, self.device)
         self.num_envs = B = int(num_envs)
         self.env_offset = int(env_offset)
         H, W = pool.shape
@@ -443,6 +452,7 @@ class SafeLifeVectorEnv(object):
         self.episode_run = episode_run
         if episode_run is not None:         # one launch behind every step() of a started run, in front of the log's
             episode_run._attach(self)
+        self.episode_history = episode_history
         self._lib = _hip.lib()
         self._sref = C.byref(s)
         # slices: boundaries at multiples of 64 envs (keeps every slice 16-byte aligned for the row kernels)
@@ -486,6 +496,8 @@ class SafeLifeVectorEnv(object):
                 t["goal_cache"] = torch.zeros(total // 4, dtype=torch.int32, device=dev)
                 s.goal_cache = t["goal_cache"].data_ptr()
                 self.goal_cache_group = int(group.value)
+        if episode_history is not None:     # two launches behind every step(): the watched envs' frames
+            episode_history._attach(self)
 
     @staticmethod
     def _level_scalars(pa, sel):
@@ -773,6 +785,8 @@ class SafeLifeVectorEnv(object):
             sched._rewind(m)
         if self.episode_log is not None:
             self.episode_log._rewind(m)
+        if self.episode_history is not None:
+            self.episode_history._rewind(m)
         self._caller_ahead = True
         return self.obs
 
@@ -793,6 +807,9 @@ class SafeLifeVectorEnv(object):
         run = getattr(self, "episode_run", None)
         if run is not None:
             raise ValueError("%s cannot drive an episode run: %s (use step())" % (what, run.STEPPERS))
+        hist = getattr(self, "episode_history", None)
+        if hist is not None:
+            raise ValueError("%s cannot drive an episode history: %s (use step())" % (what, hist.STEPPERS))
 
     def _actions(self, actions, shape):
         torch = self.torch
@@ -818,6 +835,8 @@ class SafeLifeVectorEnv(object):
         _hip.check(rc)
         if sched is not None:
             sched._after_step()
+        if self.episode_history is not None:
+            self.episode_history._after_step()
         if self.episode_run is not None:
             self.episode_run._after_step()
         if self.episode_log is not None:
@@ -1340,6 +1359,8 @@ class SafeLifeVectorEnv(object):
         q, bufs = se["queue"]
         se["queue"] = self._new_queue()               # the step kernels fill a fresh queue from here on
         self.struct.finished = se["queue"][0]
+        if self.episode_history is not None:
+            self.episode_history._queue_replaced()
         self._caller_ahead = True                     # (the fresh queue's counter is zeroed on the caller's stream)
         H, W = self.pool.shape
         cap, K = se["capacity"], _hip.SL_SE_MAX_KEYS
