@@ -1468,6 +1468,80 @@ int slhip_history_capture(const sl_episode_history *hist, const uint16_t *board,
 int slhip_history_rewind(const sl_episode_history *hist, const uint16_t *goals, const sl_env_scalars *scalars,
                          const uint8_t *mask, void *stream);
 
+/* ---- the PPO update: minibatch deal, fused clipped loss and gradients (additive again: six symbols and one struct, nothing
+ * existing changes; SL_ABI_VERSION stays where it is) --------------------------------------------------------------------------
+ * What the reference does with a training batch (training/ppo.py:145-182): PPO.calculate_loss and the minibatch loop of
+ * PPO.train_batch.  The struct lives on the HOST; every pointer inside is a device pointer the caller owns.
+ *
+ * Per minibatch row i (r = rows ? rows[i] : i the batch row behind it, a = actions[r]; f32(x) = x rounded to float32; every
+ * operation below is a float32 operation in this order, nothing fused, IEEE division, the library's logf):
+ *   pd_i     = sign(A_r) * (1 - policy[i][a] / action_prob[r])        sign(0) = 0
+ *   policy_i = |A_r| * max(pd_i, -f32(eps_policy))                    a ONE-sided clamp
+ *   vc_i     = old_values[r] + clamp(values[i] - old_values[r], -f32(eps_value), +f32(eps_value))
+ *   value_i  = max((vc_i - returns[r])^2, (values[i] - returns[r])^2)
+ *   ent_i    = sum over k in index order of (-policy[i][k]) * log(policy[i][k] + f32(1e-12))
+ * and over the minibatch, in float64 (deterministic sums of the float32 terms: a fixed tree per workgroup of 256 rows, the
+ * workgroups in index order):
+ *   P = sum(policy_i) / n, V = sum(value_i) / n, E = sum(ent_i) / n
+ *   flag = f32(E) <= f32(entropy_clip)                                the entropy bonus has a gradient
+ *   term = -f32(entropy_reg) * (flag ? E : f32(entropy_clip))
+ *   loss = P + f32(vf_coef) * V + term
+ * A row id outside [0, N) raises SL_PPO_BAD_INDEX in *status, an action outside [0, n_actions) SL_PPO_BAD_ACTION; such a row
+ * reads nothing through the bad value, adds zero to every sum (n stays the divisor), has entropy 0 and zero gradients. */
+#define SL_PPO_BAD_ACTION 1
+#define SL_PPO_BAD_INDEX 2
+#define SL_PPO_SUMS 8             /* doubles in sums_out */
+#define SL_PPO_SUM_POLICY 0       /* P */
+#define SL_PPO_SUM_VALUE 1        /* V */
+#define SL_PPO_SUM_ENTROPY 2      /* E */
+#define SL_PPO_SUM_ENTROPY_TERM 3 /* term */
+#define SL_PPO_SUM_LOSS 4         /* loss */
+#define SL_PPO_SUM_FLAG 5         /* 1.0 or 0.0 */
+#define SL_PPO_SUM_N 6            /* n */
+#define SL_PPO_SUM_LOSS_F32 7     /* NOT a double: the slot's first four bytes hold loss rounded to float32, the rest zero */
+typedef struct sl_ppo_loss {      /* 136 bytes */
+    long long n;                  /* rows of the minibatch: of values, policy and rows; >= 1 */
+    long long N;                  /* rows of the batch: of actions .. advantages; >= 1 */
+    int32_t n_actions;            /* 2 .. 32 */
+    int32_t reserved;
+    double eps_policy, eps_value, vf_coef, entropy_reg, entropy_clip;
+    const float *values;          /* [n] the model's values for the minibatch */
+    const float *policy;          /* [n, n_actions] its probabilities */
+    const long long *actions;     /* [N] */
+    const float *action_prob;     /* [N] the probability the old policy gave the action taken */
+    const float *old_values;      /* [N] */
+    const float *returns;         /* [N] */
+    const float *advantages;      /* [N] */
+    const long long *rows;        /* [n] batch row of every minibatch row, or NULL: row i is batch row i and n == N */
+    long long *status;            /* one device word, zeroed by the caller; the kernels only ever set bits (SL_PPO_*) */
+} sl_ppo_loss;
+
+/* bytes of `workspace` for a minibatch of n rows (three doubles per workgroup of 256 rows); 8-byte aligned */
+size_t slhip_ppo_workspace_bytes(long long n);
+
+/* entropy_out float32 [n]: ent_i;  sums_out double [SL_PPO_SUMS], 8-byte aligned: the SL_PPO_SUM_* above.  Two launches: the
+ * row pass and a one-workgroup finish. */
+int slhip_ppo_loss_forward(const sl_ppo_loss *loss, float *entropy_out, double *sums_out, void *workspace, void *stream);
+
+/* d_values float32 [n] and d_policy float32 [n, n_actions]: the gradients torch's autograd gives the expression above for
+ *   *grad_loss * loss + sum_i grad_entropy[i] * ent_i        (grad_loss: a device float32; grad_entropy: [n] or NULL)
+ * computed in float32 the way autograd walks the graph: mean's backward divides by f32(n), a clamp passes the gradient where its
+ * input EQUALS a bound, the elementwise maximum gives each side half on a tie, sign(0) = 0, and the entropy term has no gradient
+ * when sums[SL_PPO_SUM_FLAG] is 0.  `sums` is what slhip_ppo_loss_forward wrote for the same *loss.  One launch. */
+int slhip_ppo_loss_backward(const sl_ppo_loss *loss, const float *grad_loss, const float *grad_entropy, const double *sums,
+                            float *d_values, float *d_policy, void *stream);
+
+/* out[i] = row rows[i] of obs for i in [0, n): obs is [N, obs_bytes] opaque bytes, out [n, obs_bytes]; with out_float32 != 0 obs is
+ * uint8 and out float32 [n, obs_bytes], widened in the same pass.  Lanes move the widest of 16 / 8 / 4 / 2 / 1 bytes that divides
+ * obs_bytes and both pointers (widening: 4 / 2 / 1 bytes in, as many floats out).  A row id outside [0, N) raises SL_PPO_BAD_INDEX
+ * in *status and leaves out[i] as it was. */
+int slhip_minibatch_obs(const void *obs, long long obs_bytes, long long N, const long long *rows, long long n, void *out,
+                        int out_float32, long long *status, void *stream);
+
+/* keys[i] = z(seed, epoch, i) for i in [0, N): splitmix64's finalizer of seed + G * (epoch * 0x100000001B3 + i + 1) mod 2^64 --
+ * slhip_sample_actions' construction with the epoch as the counter.  A minibatch deal is the stable argsort of the keys. */
+int slhip_minibatch_keys(long long N, unsigned long long seed, unsigned long long epoch, unsigned long long *keys, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

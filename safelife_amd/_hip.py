@@ -43,7 +43,13 @@ EXPORTS = (
     "slhip_episode_log_run_summary_multi",
     "slhip_episode_run_start", "slhip_episode_run_harvest", "slhip_episode_run_harvest_multi", "slhip_episode_run_tickets",
     "slhip_history_capture", "slhip_history_rewind",
+    "slhip_ppo_workspace_bytes", "slhip_ppo_loss_forward", "slhip_ppo_loss_backward", "slhip_minibatch_obs",
+    "slhip_minibatch_keys",
 )
+PPO_BAD_ACTION, PPO_BAD_INDEX = 1, 2
+#: sums_out of slhip_ppo_loss_forward: the doubles' names in order; slot PPO_SUM_LOSS_F32 holds a float32, not a double
+PPO_SUMS = ("policy", "value", "entropy", "entropy_term", "loss", "flag", "n")
+PPO_SUM_LOSS_F32 = 7
 HIST_LIVE, HIST_NO_FINAL = 1, 2
 HIST_SLOT_FREE, HIST_SLOT_ENV, HIST_SLOT_ENTRY = 0, 1, 2
 HIST_MAX_WATCH, HIST_MAX_SLOTS, HIST_ORDER_WORDS = 1024, 1024, 8
@@ -240,6 +246,14 @@ class EpisodeHistory(C.Structure):
                                              "entries", "counters", "goals", "frames", "orders")])
 
 
+class PpoLoss(C.Structure):
+    """struct sl_ppo_loss (136 bytes)"""
+    _fields_ = ([("n", C.c_longlong), ("N", C.c_longlong), ("n_actions", C.c_int32), ("reserved", C.c_int32)]
+                + [(n, C.c_double) for n in ("eps_policy", "eps_value", "vf_coef", "entropy_reg", "entropy_clip")]
+                + [(n, C.c_void_p) for n in ("values", "policy", "actions", "action_prob", "old_values", "returns",
+                                             "advantages", "rows", "status")])
+
+
 class EpisodeRun(C.Structure):
     """struct sl_episode_run (80 bytes)"""
     _fields_ = ([(n, C.c_int32) for n in ("B", "G", "env_offset", "N", "L", "n_agents")]
@@ -392,6 +406,12 @@ def lib():
                                                 C.POINTER(LogWeights), _p]
         L.slhip_history_capture.argtypes = [C.POINTER(EpisodeHistory), _p, _p, _p, _p, C.POINTER(EpisodeQueue), _p, _p]
         L.slhip_history_rewind.argtypes = [C.POINTER(EpisodeHistory), _p, _p, _p, _p]
+        L.slhip_ppo_workspace_bytes.argtypes = [C.c_longlong]
+        L.slhip_ppo_workspace_bytes.restype = C.c_size_t
+        L.slhip_ppo_loss_forward.argtypes = [C.POINTER(PpoLoss), _p, _p, _p, _p]
+        L.slhip_ppo_loss_backward.argtypes = [C.POINTER(PpoLoss), _p, _p, _p, _p, _p, _p]
+        L.slhip_minibatch_obs.argtypes = [_p, C.c_longlong, C.c_longlong, _p, C.c_longlong, _p, C.c_int, _p, _p]
+        L.slhip_minibatch_keys.argtypes = [C.c_longlong, C.c_ulonglong, C.c_ulonglong, _p, _p]
         L.slhip_obs_to_policy.argtypes = [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]
         L.slhip_gather_unique_id.argtypes = [_p]
         L.slhip_gather_init.argtypes = [_p, C.c_int, C.c_int, C.POINTER(_p)]

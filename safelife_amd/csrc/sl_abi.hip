@@ -2158,4 +2158,52 @@ int slhip_history_rewind(const sl_episode_history *hist, const uint16_t *goals, 
     return err == hipSuccess ? SL_OK : hip_fail(err, "history_rewind launch");
 }
 
+static int check_ppo_loss(const sl_ppo_loss *p) {
+    if (!p) return fail(SL_E_ARG, "ppo_loss: null description");
+    if (p->n < 1 || p->N < 1) return fail(SL_E_ARG, "ppo_loss: n and N must be at least 1");
+    if (p->n_actions < 2 || p->n_actions > 32) return fail(SL_E_ARG, "ppo_loss: n_actions outside 2..32");
+    if (!p->rows && p->n != p->N) return fail(SL_E_ARG, "ppo_loss: without rows n must equal N");
+    if (!p->values || !p->policy || !p->actions || !p->action_prob || !p->old_values || !p->returns || !p->advantages ||
+        !p->status)
+        return fail(SL_E_ARG, "ppo_loss: null pointer in the description");
+    return SL_OK;
+}
+
+size_t slhip_ppo_workspace_bytes(long long n) { return n < 1 ? 0 : sl::ppo_workspace_bytes(n); }
+
+int slhip_ppo_loss_forward(const sl_ppo_loss *loss, float *entropy_out, double *sums_out, void *workspace, void *stream) {
+    if (int rc = check_ppo_loss(loss)) return rc;
+    if (!entropy_out || !sums_out || !workspace) return fail(SL_E_ARG, "ppo_loss_forward: null pointer");
+    if (((uintptr_t)sums_out | (uintptr_t)workspace) & 7) return fail(SL_E_ARG, "ppo_loss_forward: sums_out / workspace not 8-byte aligned");
+    const hipError_t err = sl::launch_ppo_loss_forward(*loss, entropy_out, sums_out, workspace, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "ppo_loss_forward launch");
+}
+
+int slhip_ppo_loss_backward(const sl_ppo_loss *loss, const float *grad_loss, const float *grad_entropy, const double *sums,
+                            float *d_values, float *d_policy, void *stream) {
+    if (int rc = check_ppo_loss(loss)) return rc;
+    if (!grad_loss || !sums || !d_values || !d_policy) return fail(SL_E_ARG, "ppo_loss_backward: null pointer");
+    const hipError_t err = sl::launch_ppo_loss_backward(*loss, grad_loss, grad_entropy, sums, d_values, d_policy,
+                                                        (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "ppo_loss_backward launch");
+}
+
+int slhip_minibatch_obs(const void *obs, long long obs_bytes, long long N, const long long *rows, long long n, void *out,
+                        int out_float32, long long *status, void *stream) {
+    if (obs_bytes < 1 || N < 1 || n < 0) return fail(SL_E_ARG, "minibatch_obs: obs_bytes and N must be at least 1, n at least 0");
+    if (n == 0) return SL_OK;
+    if (!obs || !rows || !out || !status) return fail(SL_E_ARG, "minibatch_obs: null pointer");
+    if (out_float32 && ((uintptr_t)out & 3)) return fail(SL_E_ARG, "minibatch_obs: a float32 out must be 4-byte aligned");
+    const hipError_t err = sl::launch_minibatch_obs(obs, obs_bytes, N, rows, n, out, out_float32, status, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "minibatch_obs launch");
+}
+
+int slhip_minibatch_keys(long long N, unsigned long long seed, unsigned long long epoch, unsigned long long *keys, void *stream) {
+    if (N < 0) return fail(SL_E_ARG, "minibatch_keys: N must be at least 0");
+    if (N == 0) return SL_OK;
+    if (!keys) return fail(SL_E_ARG, "minibatch_keys: null pointer");
+    const hipError_t err = sl::launch_minibatch_keys(N, seed, epoch, keys, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "minibatch_keys launch");
+}
+
 }  // extern "C"

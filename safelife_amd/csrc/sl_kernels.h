@@ -158,6 +158,16 @@ hipError_t launch_history_capture(const sl_episode_history &h, const uint16_t *b
                                   const uint8_t *active, hipStream_t stream);
 hipError_t launch_history_rewind(const sl_episode_history &h, const uint16_t *goals, const sl_env_scalars *scalars,
                                  const uint8_t *mask, hipStream_t stream);
+// the PPO update (sl_ppo.hip): the fused clipped loss and its gradients, a minibatch's observation rows, the deal's keys
+size_t ppo_workspace_bytes(long long n);
+hipError_t launch_ppo_loss_forward(const sl_ppo_loss &p, float *entropy_out, double *sums_out, void *workspace,
+                                   hipStream_t stream);
+hipError_t launch_ppo_loss_backward(const sl_ppo_loss &p, const float *grad_loss, const float *grad_entropy,
+                                    const double *sums, float *d_values, float *d_policy, hipStream_t stream);
+hipError_t launch_minibatch_obs(const void *obs, long long obs_bytes, long long N, const long long *rows, long long n,
+                                void *out, int out_float32, long long *status, hipStream_t stream);
+hipError_t launch_minibatch_keys(long long N, unsigned long long seed, unsigned long long epoch, unsigned long long *keys,
+                                 hipStream_t stream);
 // envs [e_first, e_first + e_count) of the batch; actions / reward_t / done_t are indexed [t * tstride + e]
 // with the env's index in the whole batch
 // (sl_aql.hip dispatches the same kernel from queues of the library's own: PreparedStep below)
