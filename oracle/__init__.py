@@ -448,16 +448,23 @@ class OracleMultiEnv(OracleEnv):
         super().__init__(arrays, with_obs=False, **kw)
         B, A, L = self.s.B, int(pool.n_agents), self.s.L
         self.A = A
+        if A > 1:
+            per_agent = {k: getattr(pool, "pool_agent_" + k) for k in ("locs", "required_reset", "required_step",
+                                                                        "initial_points", "table_idx")}
+        else:       # a one-agent pool keeps no pool_agent_* arrays: its single-agent ones describe agent 0
+            per_agent = {"locs": pool.pool_agent_loc, "required_reset": pool.pool_required_reset,
+                         "required_step": pool.pool_required_step, "initial_points": pool.pool_initial_points,
+                         "table_idx": pool.pool_table_idx}
         ma = self.ma = {
             "agent_loc": np.zeros((B, A, 2), np.int32), "old_value": np.zeros((B, A), np.int32),
             "required_points": np.zeros((B, A), np.int32), "initial_points": np.zeros((B, A), np.int32),
             "table_idx": np.zeros((B, A), np.int32), "is_active": np.zeros((B, A), np.uint8),
             "episode_reward": np.zeros((B, A), np.float32), "episode_length": np.zeros((B, A), np.int32),
-            "pool_agent_loc": np.ascontiguousarray(pool.pool_agent_locs, np.int32).reshape(L, A, 2),
-            "pool_required_reset": np.ascontiguousarray(pool.pool_agent_required_reset, np.int32),
-            "pool_required_step": np.ascontiguousarray(pool.pool_agent_required_step, np.int32),
-            "pool_initial_points": np.ascontiguousarray(pool.pool_agent_initial_points, np.int32),
-            "pool_table_idx": np.ascontiguousarray(pool.pool_agent_table_idx, np.int32),
+            "pool_agent_loc": np.ascontiguousarray(per_agent["locs"], np.int32).reshape(L, A, 2),
+            "pool_required_reset": np.ascontiguousarray(per_agent["required_reset"], np.int32).reshape(L, A),
+            "pool_required_step": np.ascontiguousarray(per_agent["required_step"], np.int32).reshape(L, A),
+            "pool_initial_points": np.ascontiguousarray(per_agent["initial_points"], np.int32).reshape(L, A),
+            "pool_table_idx": np.ascontiguousarray(per_agent["table_idx"], np.int32).reshape(L, A),
             "reward": np.zeros((B, A), np.float32), "done": np.zeros((B, A), np.uint8), "success": np.zeros((B, A), np.uint8),
         }
         vh, vw, nc = self.s.view_h, self.s.view_w, self.s.n_channels
