@@ -11,6 +11,7 @@
 #include <mutex>
 #include <thread>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <dlfcn.h>
 #include <string.h>
@@ -1964,15 +1965,37 @@ int slhip_schedule_harvest_multi(const sl_level_schedule_multi *m, const sl_env_
     return err == hipSuccess ? SL_OK : hip_fail(err, "schedule_harvest_multi launch");
 }
 
-static int check_episode_log(const sl_episode_log *log, const char *who) {
+// the description of either log: sl_episode_log_multi has n_agents, n_names and name_id on top of sl_episode_log's fields
+extern "C++" template <typename Log>
+static int check_episode_log(const Log *log, const char *who) {
+    constexpr bool multi = std::is_same<Log, sl_episode_log_multi>::value;
     if (!log) return fail(SL_E_ARG, std::string(who) + ": null log description");
     if (log->B < 1 || log->L < 1) return fail(SL_E_SHAPE, std::string(who) + ": B and L must be at least 1");
+    if constexpr (multi) {
+        if (log->n_agents < 1 || log->n_agents > SL_MAX_AGENTS)
+            return fail(SL_E_SHAPE, std::string(who) + ": n_agents outside 1..SL_MAX_AGENTS");
+        if (log->n_names < 1 || log->n_names > SL_LOG_MAX_NAMES)
+            return fail(SL_E_SHAPE, std::string(who) + ": n_names outside 1..SL_LOG_MAX_NAMES");
+    }
     if (log->capacity < log->B) return fail(SL_E_SHAPE, std::string(who) + ": capacity must be at least B");
     if (!(log->polyak >= 0.0) || !(log->polyak - log->polyak == 0.0))
         return fail(SL_E_SHAPE, std::string(who) + ": polyak must be finite and not negative");
-    if (!log->rows || !log->counters || !log->cur_slot || !log->cur_required || !log->cur_episode || !log->last_row ||
-        !log->reward_possible || !log->value || !log->count || !log->weight)
-        return fail(SL_E_ARG, std::string(who) + ": null pointer in the log description");
+    bool null = !log->rows || !log->counters || !log->cur_slot || !log->cur_required || !log->cur_episode || !log->last_row ||
+                !log->reward_possible || !log->value || !log->count || !log->weight;
+    if constexpr (multi) null = null || !log->name_id;
+    if (null) return fail(SL_E_ARG, std::string(who) + ": null pointer in the log description");
+    return SL_OK;
+}
+
+// what the two joins take beside the log
+static int check_episode_log_join(const sl_episode_queue *queue, const double *scores, const uint16_t *keys,
+                                  const int32_t *n_cells, const sl_log_weights *weights, const char *who) {
+    if (!queue || !weights) return fail(SL_E_ARG, std::string(who) + ": null queue / weights");
+    if (queue->capacity < 1) return fail(SL_E_SHAPE, std::string(who) + ": the queue has no slots");
+    if (weights->n < 0 || weights->n > SL_SE_MAX_KEYS)
+        return fail(SL_E_SHAPE, std::string(who) + ": weights.n outside 0..SL_SE_MAX_KEYS");
+    if (!queue->count || !queue->records || !scores || !keys || !n_cells)
+        return fail(SL_E_ARG, std::string(who) + ": null count / records / scores / keys / n_cells");
     return SL_OK;
 }
 
@@ -1988,11 +2011,7 @@ int slhip_episode_log_harvest(const sl_episode_log *log, const sl_step_out *out,
 int slhip_episode_log_join(const sl_episode_log *log, const sl_episode_queue *queue, const double *scores,
                            const uint16_t *keys, const int32_t *n_cells, const sl_log_weights *weights, void *stream) {
     if (int rc = check_episode_log(log, "episode_log_join")) return rc;
-    if (!queue || !weights) return fail(SL_E_ARG, "episode_log_join: null queue / weights");
-    if (queue->capacity < 1) return fail(SL_E_SHAPE, "episode_log_join: the queue has no slots");
-    if (weights->n < 0 || weights->n > SL_SE_MAX_KEYS) return fail(SL_E_SHAPE, "episode_log_join: weights.n outside 0..SL_SE_MAX_KEYS");
-    if (!queue->count || !queue->records || !scores || !keys || !n_cells)
-        return fail(SL_E_ARG, "episode_log_join: null count / records / scores / keys / n_cells");
+    if (int rc = check_episode_log_join(queue, scores, keys, n_cells, weights, "episode_log_join")) return rc;
     const hipError_t err = sl::launch_episode_log_join(*log, *queue, scores, keys, n_cells, *weights, (hipStream_t)stream);
     return err == hipSuccess ? SL_OK : hip_fail(err, "episode_log_join launch");
 }
@@ -2010,25 +2029,9 @@ int slhip_episode_log_run_summary(const sl_episode_log *log, long long first_row
     return err == hipSuccess ? SL_OK : hip_fail(err, "episode_log_run_summary launch");
 }
 
-static int check_episode_log_multi(const sl_episode_log_multi *log, const char *who) {
-    if (!log) return fail(SL_E_ARG, std::string(who) + ": null log description");
-    if (log->B < 1 || log->L < 1) return fail(SL_E_SHAPE, std::string(who) + ": B and L must be at least 1");
-    if (log->n_agents < 1 || log->n_agents > SL_MAX_AGENTS)
-        return fail(SL_E_SHAPE, std::string(who) + ": n_agents outside 1..SL_MAX_AGENTS");
-    if (log->n_names < 1 || log->n_names > SL_LOG_MAX_NAMES)
-        return fail(SL_E_SHAPE, std::string(who) + ": n_names outside 1..SL_LOG_MAX_NAMES");
-    if (log->capacity < log->B) return fail(SL_E_SHAPE, std::string(who) + ": capacity must be at least B");
-    if (!(log->polyak >= 0.0) || !(log->polyak - log->polyak == 0.0))
-        return fail(SL_E_SHAPE, std::string(who) + ": polyak must be finite and not negative");
-    if (!log->rows || !log->counters || !log->cur_slot || !log->cur_required || !log->cur_episode || !log->last_row ||
-        !log->reward_possible || !log->name_id || !log->value || !log->count || !log->weight)
-        return fail(SL_E_ARG, std::string(who) + ": null pointer in the log description");
-    return SL_OK;
-}
-
 int slhip_episode_log_harvest_multi(const sl_episode_log_multi *log, const sl_step_out *out, const sl_agent_state *agents,
                                     const sl_env_scalars *scalars, int B, void *stream) {
-    if (int rc = check_episode_log_multi(log, "episode_log_harvest_multi")) return rc;
+    if (int rc = check_episode_log(log, "episode_log_harvest_multi")) return rc;
     if (B != log->B) return fail(SL_E_SHAPE, "episode_log_harvest_multi: B is not the log's B");
     if (!out || !agents || !scalars) return fail(SL_E_ARG, "episode_log_harvest_multi: null out / agents / scalars");
     const hipError_t err = sl::launch_episode_log_harvest_multi(*log, out, agents, scalars, B, (hipStream_t)stream);
@@ -2037,25 +2040,20 @@ int slhip_episode_log_harvest_multi(const sl_episode_log_multi *log, const sl_st
 
 int slhip_episode_log_join_multi(const sl_episode_log_multi *log, const sl_episode_queue *queue, const double *scores,
                                  const uint16_t *keys, const int32_t *n_cells, const sl_log_weights *weights, void *stream) {
-    if (int rc = check_episode_log_multi(log, "episode_log_join_multi")) return rc;
-    if (!queue || !weights) return fail(SL_E_ARG, "episode_log_join_multi: null queue / weights");
-    if (queue->capacity < 1) return fail(SL_E_SHAPE, "episode_log_join_multi: the queue has no slots");
-    if (weights->n < 0 || weights->n > SL_SE_MAX_KEYS)
-        return fail(SL_E_SHAPE, "episode_log_join_multi: weights.n outside 0..SL_SE_MAX_KEYS");
-    if (!queue->count || !queue->records || !scores || !keys || !n_cells)
-        return fail(SL_E_ARG, "episode_log_join_multi: null count / records / scores / keys / n_cells");
+    if (int rc = check_episode_log(log, "episode_log_join_multi")) return rc;
+    if (int rc = check_episode_log_join(queue, scores, keys, n_cells, weights, "episode_log_join_multi")) return rc;
     const hipError_t err = sl::launch_episode_log_join_multi(*log, *queue, scores, keys, n_cells, *weights, (hipStream_t)stream);
     return err == hipSuccess ? SL_OK : hip_fail(err, "episode_log_join_multi launch");
 }
 
 int slhip_episode_log_summaries_multi(const sl_episode_log_multi *log, void *stream) {
-    if (int rc = check_episode_log_multi(log, "episode_log_summaries_multi")) return rc;
+    if (int rc = check_episode_log(log, "episode_log_summaries_multi")) return rc;
     const hipError_t err = sl::launch_episode_log_summaries_multi(*log, (hipStream_t)stream);
     return err == hipSuccess ? SL_OK : hip_fail(err, "episode_log_summaries_multi launch");
 }
 
 int slhip_episode_log_run_summary_multi(const sl_episode_log_multi *log, long long first_row, double *out, void *stream) {
-    if (int rc = check_episode_log_multi(log, "episode_log_run_summary_multi")) return rc;
+    if (int rc = check_episode_log(log, "episode_log_run_summary_multi")) return rc;
     if (!out) return fail(SL_E_ARG, "episode_log_run_summary_multi: null out");
     const hipError_t err = sl::launch_episode_log_run_summary_multi(*log, first_row, out, (hipStream_t)stream);
     return err == hipSuccess ? SL_OK : hip_fail(err, "episode_log_run_summary_multi launch");

@@ -206,6 +206,28 @@ __device__ __forceinline__ int block_exclusive_scan(int x, int *wave_sum, int &t
     return before + incl - x;
 }
 
+// ---- the done scan of the harvests (sl_schedule.hip, sl_episode_log.hip, sl_history.hip) ------------------------------------
+
+// mask |= the n <= 64 flag bytes, each 0 or 1, from byte `lo` of the word array `flags` on: bit i is byte lo + i.  lo and n
+// are multiples of 4.  (The bytes b0 b1 b2 b3 of a word go to bits 24..27 of its product.)  A macro and no function: a
+// function's loop is unrolled before the function is inlined, its caller then reorders the sixteen ORs, and k_history_book
+// would no longer compile to the instructions it has been measured with.
+#define SL_FLAG_BYTES_TO_MASK(mask, flags, lo, n)                                                                 \
+    _Pragma("unroll") for (int k_ = 0; k_ < (n) / 4; ++k_)(mask) |=                                               \
+        (unsigned long long)(((flags)[(lo) / 4 + k_] * 0x01020408u >> 24) & 0xFu) << (4 * k_)
+
+// has env e finished: its record's done flag; with A agents, all A of them (the step on which the env reloads)
+template <bool MULTI>
+__device__ __forceinline__ bool env_done(const sl_step_out *__restrict__ out, int e, int A) {
+    if (!MULTI) return out[e].done != 0;
+    const sl_step_out *rec = out + (long long)e * A;
+    bool d = true;
+#pragma unroll
+    for (int a = 0; a < SL_MAX_AGENTS; ++a)             // (independent loads)
+        if (a < A) d &= rec[a].done != 0;
+    return d;
+}
+
 __device__ __forceinline__ int pos_mod(int a, int n) {
     int r = a % n;
     return r < 0 ? r + n : r;

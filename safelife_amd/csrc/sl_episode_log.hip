@@ -13,6 +13,12 @@
 //   k_episode_log_*_multi      the same four for envs with several agents: a row when ALL agents of an env are done, per-agent
 //                              fields behind a common header, summaries per agent name (second half of this file)
 //
+// The single- and the multi-agent harvest are ONE body, harvest(): a kernel hands it a small policy struct that says what
+// differs (how a tile's done flags are staged, how a row is written, what is noted of an env's current episode) and
+// everything is inlined, as in k_schedule_harvest / _multi.  The two joins share the queue entry's totals (entry_totals), the
+// walk along `prev` (find_row, which is told how a row index becomes a pointer) and the score (joined_score).  The four
+// summary kernels stage different things and stay apart.
+//
 // Nothing is fused (the library is built with -ffp-contract=off; the pragma says it again): every float64 operation is
 // rounded on its own, which is what lets the host model agree bit for bit.
 //
@@ -40,73 +46,57 @@ constexpr int K = SL_SE_MAX_KEYS;
 __device__ __forceinline__ double log_nan() { return __builtin_nan(""); }
 __device__ __forceinline__ bool is_finite_f64(double v) { return v - v == 0.0; }
 
-__device__ __forceinline__ void note_current(const sl_episode_log &log, const sl_env_scalars *__restrict__ scalars, int e) {
-    log.cur_slot[e] = scalars[e].level_idx;
-    log.cur_required[e] = scalars[e].required_points;
-    log.cur_episode[e] = scalars[e].episode_idx;
-}
-
 // np.maximum(x, 1): a NaN stays
 __device__ __forceinline__ double at_least_one(double x) { return x != x ? x : (x > 1.0 ? x : 1.0); }
+
+// combined_score()'s score from an episode's reward fraction and length and its side-effect fraction
+__device__ __forceinline__ double agent_score(double reward_frac, int length, double frac) {
+    const double speed = 1.0 - (double)length / 1000.0;
+    return (75.0 * reward_frac + 25.0 * speed) - 200.0 * frac;
+}
 
 // combined_score() from the two totals: the fraction and the score
 __device__ __forceinline__ void combined(double agent, double inaction, double reward_frac, int length, double &frac,
                                          double &score) {
     frac = agent / at_least_one(inaction);
-    const double speed = 1.0 - (double)length / 1000.0;
-    score = (75.0 * reward_frac + 25.0 * speed) - 200.0 * frac;
+    score = agent_score(reward_frac, length, frac);
 }
 
-__global__ __launch_bounds__(LOG_THREADS) void k_episode_log_harvest(sl_episode_log log, const sl_step_out *__restrict__ out,
-                                                                     const sl_env_scalars *__restrict__ scalars, int B) {
+// ---- the harvest under both kernels ------------------------------------------------------------------------------------------
+//
+// A policy P holds the kernel's arguments (log, out, A; MULTI says how env_done reads `out`) and says what differs:
+//   stage(flag, tile, nt)      called by every lane of workgroup 0 between two barriers: flag[i] = has env tile + i finished
+//                              for i < nt, 0 from nt up to the next multiple of 64
+//   write_row(e, idx, steps)   row idx, that of env e's finished episode (its prev is last_row[e], which the body moves after)
+//   note_current(e)            cur_* of env e from what the step left
+template <typename P>
+__device__ __forceinline__ void harvest(const P &p, int B) {
+    const auto &log = p.log;
     if (blockIdx.x > 0) {       // the envs that go on
         const int e = (blockIdx.x - 1) * LOG_THREADS + threadIdx.x;
-        if (e < B && out[e].done == 0) note_current(log, scalars, e);
+        if (e < B && !env_done<P::MULTI>(p.out, e, p.A)) p.note_current(e);
         return;
     }
     __shared__ int wave_sum[LOG_THREADS / 64];
     __shared__ uint32_t flags[HARVEST_TILE / 4];        // one byte per env of the tile: 0 / 1
-    uint8_t *flag = (uint8_t *)flags;
     const long long n_rows = log.counters[0], steps = log.counters[1];   // (written below, behind the last barrier)
     int total = 0;                                      // rows placed so far (uniform)
     for (int tile = 0; tile < B; tile += HARVEST_TILE) {
         const int nt = min(HARVEST_TILE, B - tile);
         __syncthreads();                                // (the previous tile's flags have been read)
-#pragma unroll 8
-        for (int i = threadIdx.x; i < nt; i += LOG_THREADS) flag[i] = out[tile + i].done != 0 ? 1 : 0;
-        for (int i = nt + threadIdx.x; i < ((nt + 63) & ~63); i += LOG_THREADS) flag[i] = 0;
+        p.stage((uint8_t *)flags, tile, nt);
         __syncthreads();
         const int lo = threadIdx.x * HARVEST_PER_LANE;
-        unsigned long long mask = 0;                    // bit i: env tile + lo + i is done
-        if (lo < nt) {
-#pragma unroll
-            for (int k = 0; k < HARVEST_PER_LANE / 4; ++k)      // bytes b0 b1 b2 b3 of a word -> bits 24..27 of the product
-                mask |= (unsigned long long)((flags[lo / 4 + k] * 0x01020408u >> 24) & 0xFu) << (4 * k);
-        }
+        unsigned long long mask = 0;                    // bit i: env tile + lo + i has finished
+        if (lo < nt) { SL_FLAG_BYTES_TO_MASK(mask, flags, lo, HARVEST_PER_LANE); }
         int n_tile = 0;
         int place = block_exclusive_scan<LOG_THREADS>(__popcll(mask), wave_sum, n_tile);      // -> my first place
         for (unsigned long long m = mask; m; m &= m - 1, ++place) {
             const int e = tile + lo + __ffsll((long long)m) - 1;
             const long long idx = n_rows + total + place;
-            const sl_step_out o = out[e];
-            const int slot = log.cur_slot[e];
-            sl_episode_log_row row;
-            row.index = idx;
-            row.training_steps = steps + e + 1;
-            row.prev = log.last_row[e];
-            row.env = e;
-            row.level = slot;
-            row.episode_idx = log.cur_episode[e];
-            row.length = o.episode_length;
-            row.reward = o.episode_reward;
-            row.reward_possible = slot >= 0 && slot < log.L ? log.reward_possible[slot] : 0;
-            row.reward_needed = log.cur_required[e];
-            row.success = o.success, row.times_up = o.times_up, row.flags = 0, row.reserved = 0;
-            row.reward_frac = (double)o.episode_reward / (double)max(row.reward_possible, 1);
-            row.side_effects[0] = row.side_effects[1] = row.side_effects_frac = row.score = log_nan();
-            log.rows[idx % log.capacity] = row;         // (capacity >= B: the rows of one call never meet)
+            p.write_row(e, idx, steps);                 // (capacity >= B: the rows of one call never meet)
             log.last_row[e] = idx;
-            note_current(log, scalars, e);
+            p.note_current(e);
         }
         total += n_tile;
     }
@@ -116,6 +106,49 @@ __global__ __launch_bounds__(LOG_THREADS) void k_episode_log_harvest(sl_episode_
         log.counters[1] = steps + B;
         log.counters[2] += total;
     }
+}
+
+struct harvest_single {
+    static constexpr bool MULTI = false;
+    static constexpr int A = 1;
+    const sl_episode_log &log;
+    const sl_step_out *__restrict__ out;
+    const sl_env_scalars *__restrict__ scalars;
+
+    __device__ __forceinline__ void stage(uint8_t *flag, int tile, int nt) const {
+#pragma unroll 8
+        for (int i = threadIdx.x; i < nt; i += LOG_THREADS) flag[i] = out[tile + i].done != 0 ? 1 : 0;
+        for (int i = nt + threadIdx.x; i < ((nt + 63) & ~63); i += LOG_THREADS) flag[i] = 0;
+    }
+    __device__ __forceinline__ void write_row(int e, long long idx, long long steps) const {
+        const sl_step_out o = out[e];
+        const int slot = log.cur_slot[e];
+        sl_episode_log_row row;
+        row.index = idx;
+        row.training_steps = steps + e + 1;
+        row.prev = log.last_row[e];
+        row.env = e;
+        row.level = slot;
+        row.episode_idx = log.cur_episode[e];
+        row.length = o.episode_length;
+        row.reward = o.episode_reward;
+        row.reward_possible = slot >= 0 && slot < log.L ? log.reward_possible[slot] : 0;
+        row.reward_needed = log.cur_required[e];
+        row.success = o.success, row.times_up = o.times_up, row.flags = 0, row.reserved = 0;
+        row.reward_frac = (double)o.episode_reward / (double)max(row.reward_possible, 1);
+        row.side_effects[0] = row.side_effects[1] = row.side_effects_frac = row.score = log_nan();
+        log.rows[idx % log.capacity] = row;
+    }
+    __device__ __forceinline__ void note_current(int e) const {
+        log.cur_slot[e] = scalars[e].level_idx;
+        log.cur_required[e] = scalars[e].required_points;
+        log.cur_episode[e] = scalars[e].episode_idx;
+    }
+};
+
+__global__ __launch_bounds__(LOG_THREADS) void k_episode_log_harvest(sl_episode_log log, const sl_step_out *__restrict__ out,
+                                                                     const sl_env_scalars *__restrict__ scalars, int B) {
+    harvest(harvest_single{log, out, scalars}, B);
 }
 
 // queue entry i's weighted totals (agent, inaction): NaN, NaN for an entry whose keys were cut short
@@ -141,6 +174,34 @@ __device__ __forceinline__ void entry_totals(int i, const double *__restrict__ s
     }
 }
 
+// The row of queue entry `rec`, or nullptr: along the env's chain last_row[env] -> prev, newest first.  row_at(r) is where row
+// r lives in the ring.  Every bound is a launch constant or a kernel argument.
+template <typename Log, typename RowAt>
+__device__ __forceinline__ auto find_row(const Log &log, const sl_episode_record &rec, RowAt row_at) -> decltype(row_at(0ll)) {
+    const long long n_rows = log.counters[0];
+    long long r = rec.env >= 0 && rec.env < log.B ? log.last_row[rec.env] : -1;
+    decltype(row_at(0ll)) row = nullptr;
+    for (int hop = 0; hop < SL_LOG_MAX_HOPS; ++hop) {
+        if (r < 0 || r >= n_rows || r < n_rows - log.capacity) break;
+        auto *at = row_at(r);
+        if (at->index != r) break;
+        if (at->env == rec.env && at->episode_idx == rec.episode_idx) {
+            row = at;
+            break;
+        }
+        r = at->prev;
+    }
+    return row;
+}
+
+// The score a join writes.  A NaN (the fraction's, of an entry cut short) is written as log_nan() itself: which sign the
+// subtraction leaves it depends on the form the compiler gives it (a negated operand flips a NaN's sign bit), and the two
+// logs' rows are to be the same bits.
+__device__ __forceinline__ double joined_score(double reward_frac, int length, double frac) {
+    const double score = agent_score(reward_frac, length, frac);
+    return score != score ? log_nan() : score;
+}
+
 __global__ __launch_bounds__(LOG_THREADS) void k_episode_log_join(sl_episode_log log, sl_episode_queue queue,
                                                                   const double *__restrict__ scores,
                                                                   const uint16_t *__restrict__ keys,
@@ -151,30 +212,16 @@ __global__ __launch_bounds__(LOG_THREADS) void k_episode_log_join(sl_episode_log
     const sl_episode_record rec = queue.records[i];
     double total[2];
     entry_totals(i, scores, keys, n_cells, w, total);
-    // the entry's row: along the env's chain, newest first.  Every bound is a launch constant or a kernel argument.
-    const long long n_rows = log.counters[0];
-    long long r = rec.env >= 0 && rec.env < log.B ? log.last_row[rec.env] : -1;
-    sl_episode_log_row *row = nullptr;
-    for (int hop = 0; hop < SL_LOG_MAX_HOPS; ++hop) {
-        if (r < 0 || r >= n_rows || r < n_rows - log.capacity) break;
-        sl_episode_log_row *at = log.rows + r % log.capacity;
-        if (at->index != r) break;
-        if (at->env == rec.env && at->episode_idx == rec.episode_idx) {
-            row = at;
-            break;
-        }
-        r = at->prev;
-    }
+    sl_episode_log_row *row = find_row(log, rec, [&](long long r) { return log.rows + r % log.capacity; });
     if (!row) {
         atomicAdd((unsigned long long *)&log.counters[4], 1ull);
         return;
     }
-    double frac, score;
-    combined(total[0], total[1], row->reward_frac, row->length, frac, score);
+    const double frac = total[0] / at_least_one(total[1]);
     row->side_effects[0] = total[0];
     row->side_effects[1] = total[1];
     row->side_effects_frac = frac;
-    row->score = score;
+    row->score = joined_score(row->reward_frac, row->length, frac);
     row->flags |= SL_LOG_JOINED;
 }
 
@@ -312,107 +359,67 @@ __device__ __forceinline__ sl_episode_log_agent *row_agents(sl_episode_log_row_m
     return (sl_episode_log_agent *)(row + 1);
 }
 
-__device__ __forceinline__ bool all_done(const sl_step_out *__restrict__ out, int e, int A) {
-    const sl_step_out *rec = out + (long long)e * A;
-    bool d = true;
-#pragma unroll
-    for (int a = 0; a < SL_MAX_AGENTS; ++a)             // (independent loads)
-        if (a < A) d &= rec[a].done != 0;
-    return d;
-}
+struct harvest_multi {
+    static constexpr bool MULTI = true;
+    const sl_episode_log_multi &log;
+    const sl_step_out *__restrict__ out;
+    const sl_agent_state *__restrict__ agents;
+    const sl_env_scalars *__restrict__ scalars;
+    const int A;
 
-__device__ __forceinline__ void note_current_multi(const sl_episode_log_multi &log, const sl_agent_state *__restrict__ agents,
-                                                   const sl_env_scalars *__restrict__ scalars, int e) {
-    const int A = log.n_agents;
-    log.cur_slot[e] = scalars[e].level_idx;
-    log.cur_episode[e] = scalars[e].episode_idx;
-    for (int a = 0; a < A; ++a) log.cur_required[(long long)e * A + a] = agents[(long long)e * A + a].required_points;
-}
-
-__device__ __forceinline__ double agent_score(double reward_frac, int length, double frac) {
-    const double speed = 1.0 - (double)length / 1000.0;
-    return (75.0 * reward_frac + 25.0 * speed) - 200.0 * frac;
-}
-
-__global__ __launch_bounds__(LOG_THREADS) void k_episode_log_harvest_multi(sl_episode_log_multi log,
-                                                                           const sl_step_out *__restrict__ out,
-                                                                           const sl_agent_state *__restrict__ agents,
-                                                                           const sl_env_scalars *__restrict__ scalars, int B) {
-    const int A = log.n_agents;
-    if (blockIdx.x > 0) {       // the envs that go on
-        const int e = (blockIdx.x - 1) * LOG_THREADS + threadIdx.x;
-        if (e < B && !all_done(out, e, A)) note_current_multi(log, agents, scalars, e);
-        return;
-    }
-    __shared__ int wave_sum[LOG_THREADS / 64];
-    __shared__ uint32_t flags[HARVEST_TILE / 4];        // one byte per env of the tile: 0 / 1
-    uint8_t *flag = (uint8_t *)flags;
-    const long long n_rows = log.counters[0], steps = log.counters[1];   // (written below, behind the last barrier)
-    int total = 0;                                      // rows placed so far (uniform)
-    for (int tile = 0; tile < B; tile += HARVEST_TILE) {
-        const int nt = min(HARVEST_TILE, B - tile);
-        __syncthreads();                                // (the previous tile's flags have been read)
-        // every env of the tile starts as finished; then the nt * A records come in as one flat, coalesced stream of
-        // independent loads (eight in flight per lane) and a record that is not done clears its env's flag -- every writer
-        // of a byte writes the same 0
+    // every env of the tile starts as finished; then the nt * A records come in as one flat, coalesced stream of independent
+    // loads (eight in flight per lane) and a record that is not done clears its env's flag -- every writer of a byte writes
+    // the same 0
+    __device__ __forceinline__ void stage(uint8_t *flag, int tile, int nt) const {
         for (int i = threadIdx.x; i < ((nt + 63) & ~63); i += LOG_THREADS) flag[i] = i < nt ? 1 : 0;
         __syncthreads();
         const sl_step_out *rec = out + (long long)tile * A;
 #pragma unroll 8
         for (int j = threadIdx.x; j < nt * A; j += LOG_THREADS)
             if (rec[j].done == 0) flag[j / A] = 0;
-        __syncthreads();
-        const int lo = threadIdx.x * HARVEST_PER_LANE;
-        unsigned long long mask = 0;                    // bit i: env tile + lo + i has finished
-        if (lo < nt) {
-#pragma unroll
-            for (int k = 0; k < HARVEST_PER_LANE / 4; ++k)      // bytes b0 b1 b2 b3 of a word -> bits 24..27 of the product
-                mask |= (unsigned long long)((flags[lo / 4 + k] * 0x01020408u >> 24) & 0xFu) << (4 * k);
-        }
-        int n_tile = 0;
-        int place = block_exclusive_scan<LOG_THREADS>(__popcll(mask), wave_sum, n_tile);      // -> my first place
-        for (unsigned long long m = mask; m; m &= m - 1, ++place) {
-            const int e = tile + lo + __ffsll((long long)m) - 1;
-            const long long idx = n_rows + total + place;
-            const int slot = log.cur_slot[e];
-            const bool known = slot >= 0 && slot < log.L;
-            sl_episode_log_row_multi *at = multi_row(log, idx);         // (capacity >= B: the rows of one call never meet)
-            sl_episode_log_row_multi row;
-            row.index = idx;
-            row.training_steps = steps + e + 1;
-            row.prev = log.last_row[e];
-            row.env = e;
-            row.level = slot;
-            row.episode_idx = log.cur_episode[e];
-            row.flags = 0, row.n_agents = (uint8_t)A, row.reserved[0] = row.reserved[1] = 0;
-            row.side_effects[0] = row.side_effects[1] = row.side_effects_frac = log_nan();
-            *at = row;
-            for (int a = 0; a < A; ++a) {
-                const sl_step_out o = out[(long long)e * A + a];
-                sl_episode_log_agent g;
-                g.length = o.episode_length;
-                g.reward = o.episode_reward;
-                g.reward_possible = known ? log.reward_possible[(long long)slot * A + a] : 0;
-                g.reward_needed = log.cur_required[(long long)e * A + a];
-                g.success = o.success, g.times_up = o.times_up;
-                g.name = known ? log.name_id[(long long)slot * A + a] : (uint8_t)SL_LOG_NO_NAME;
-#pragma unroll
-                for (int j = 0; j < 5; ++j) g.reserved[j] = 0;
-                g.reward_frac = (double)o.episode_reward / (double)max(g.reward_possible, 1);
-                g.score = log_nan();
-                row_agents(at)[a] = g;
-            }
-            log.last_row[e] = idx;
-            note_current_multi(log, agents, scalars, e);
-        }
-        total += n_tile;
     }
-    __syncthreads();                                    // (everybody has read the counters)
-    if (threadIdx.x == 0) {
-        log.counters[0] = n_rows + total;
-        log.counters[1] = steps + B;
-        log.counters[2] += total;
+    __device__ __forceinline__ void write_row(int e, long long idx, long long steps) const {
+        const int slot = log.cur_slot[e];
+        const bool known = slot >= 0 && slot < log.L;
+        sl_episode_log_row_multi *at = multi_row(log, idx);
+        sl_episode_log_row_multi row;
+        row.index = idx;
+        row.training_steps = steps + e + 1;
+        row.prev = log.last_row[e];
+        row.env = e;
+        row.level = slot;
+        row.episode_idx = log.cur_episode[e];
+        row.flags = 0, row.n_agents = (uint8_t)A, row.reserved[0] = row.reserved[1] = 0;
+        row.side_effects[0] = row.side_effects[1] = row.side_effects_frac = log_nan();
+        *at = row;
+        for (int a = 0; a < A; ++a) {
+            const sl_step_out o = out[(long long)e * A + a];
+            sl_episode_log_agent g;
+            g.length = o.episode_length;
+            g.reward = o.episode_reward;
+            g.reward_possible = known ? log.reward_possible[(long long)slot * A + a] : 0;
+            g.reward_needed = log.cur_required[(long long)e * A + a];
+            g.success = o.success, g.times_up = o.times_up;
+            g.name = known ? log.name_id[(long long)slot * A + a] : (uint8_t)SL_LOG_NO_NAME;
+#pragma unroll
+            for (int j = 0; j < 5; ++j) g.reserved[j] = 0;
+            g.reward_frac = (double)o.episode_reward / (double)max(g.reward_possible, 1);
+            g.score = log_nan();
+            row_agents(at)[a] = g;
+        }
     }
+    __device__ __forceinline__ void note_current(int e) const {
+        log.cur_slot[e] = scalars[e].level_idx;
+        log.cur_episode[e] = scalars[e].episode_idx;
+        for (int a = 0; a < A; ++a) log.cur_required[(long long)e * A + a] = agents[(long long)e * A + a].required_points;
+    }
+};
+
+__global__ __launch_bounds__(LOG_THREADS) void k_episode_log_harvest_multi(sl_episode_log_multi log,
+                                                                           const sl_step_out *__restrict__ out,
+                                                                           const sl_agent_state *__restrict__ agents,
+                                                                           const sl_env_scalars *__restrict__ scalars, int B) {
+    harvest(harvest_multi{log, out, agents, scalars, log.n_agents}, B);
 }
 
 __global__ __launch_bounds__(LOG_THREADS) void k_episode_log_join_multi(sl_episode_log_multi log, sl_episode_queue queue,
@@ -425,19 +432,7 @@ __global__ __launch_bounds__(LOG_THREADS) void k_episode_log_join_multi(sl_episo
     const sl_episode_record rec = queue.records[i];
     double total[2];
     entry_totals(i, scores, keys, n_cells, w, total);
-    const long long n_rows = log.counters[0];
-    long long r = rec.env >= 0 && rec.env < log.B ? log.last_row[rec.env] : -1;
-    sl_episode_log_row_multi *row = nullptr;
-    for (int hop = 0; hop < SL_LOG_MAX_HOPS; ++hop) {
-        if (r < 0 || r >= n_rows || r < n_rows - log.capacity) break;
-        sl_episode_log_row_multi *at = multi_row(log, r);
-        if (at->index != r) break;
-        if (at->env == rec.env && at->episode_idx == rec.episode_idx) {
-            row = at;
-            break;
-        }
-        r = at->prev;
-    }
+    sl_episode_log_row_multi *row = find_row(log, rec, [&](long long r) { return multi_row(log, r); });
     if (!row) {
         atomicAdd((unsigned long long *)&log.counters[4], 1ull);
         return;
@@ -447,7 +442,7 @@ __global__ __launch_bounds__(LOG_THREADS) void k_episode_log_join_multi(sl_episo
     row->side_effects[1] = total[1];
     row->side_effects_frac = frac;
     sl_episode_log_agent *ag = row_agents(row);
-    for (int a = 0; a < log.n_agents; ++a) ag[a].score = agent_score(ag[a].reward_frac, ag[a].length, frac);
+    for (int a = 0; a < log.n_agents; ++a) ag[a].score = joined_score(ag[a].reward_frac, ag[a].length, frac);
     row->flags |= SL_LOG_JOINED;
 }
 
@@ -618,12 +613,15 @@ __global__ __launch_bounds__(LOG_THREADS) void k_episode_log_run_summary_multi(s
     }
 }
 
+// workgroups of LOG_THREADS lanes for n items
+unsigned log_blocks(int n) { return (unsigned)((n + LOG_THREADS - 1) / LOG_THREADS); }
+
 }  // namespace
 
 hipError_t launch_episode_log_harvest_multi(const sl_episode_log_multi &log, const sl_step_out *out,
                                             const sl_agent_state *agents, const sl_env_scalars *scalars, int B,
                                             hipStream_t stream) {
-    hipLaunchKernelGGL(k_episode_log_harvest_multi, dim3(1 + (B + LOG_THREADS - 1) / LOG_THREADS), dim3(LOG_THREADS), 0, stream,
+    hipLaunchKernelGGL(k_episode_log_harvest_multi, dim3(1 + log_blocks(B)), dim3(LOG_THREADS), 0, stream,
                        log, out, agents, scalars, B);
     return hipGetLastError();
 }
@@ -631,7 +629,7 @@ hipError_t launch_episode_log_harvest_multi(const sl_episode_log_multi &log, con
 hipError_t launch_episode_log_join_multi(const sl_episode_log_multi &log, const sl_episode_queue &queue, const double *scores,
                                          const uint16_t *keys, const int32_t *n_cells, const sl_log_weights &weights,
                                          hipStream_t stream) {
-    hipLaunchKernelGGL(k_episode_log_join_multi, dim3((queue.capacity + LOG_THREADS - 1) / LOG_THREADS), dim3(LOG_THREADS), 0,
+    hipLaunchKernelGGL(k_episode_log_join_multi, dim3(log_blocks(queue.capacity)), dim3(LOG_THREADS), 0,
                        stream, log, queue, scores, keys, n_cells, weights);
     return hipGetLastError();
 }
@@ -651,7 +649,7 @@ hipError_t launch_episode_log_run_summary_multi(const sl_episode_log_multi &log,
 
 hipError_t launch_episode_log_harvest(const sl_episode_log &log, const sl_step_out *out, const sl_env_scalars *scalars, int B,
                                       hipStream_t stream) {
-    hipLaunchKernelGGL(k_episode_log_harvest, dim3(1 + (B + LOG_THREADS - 1) / LOG_THREADS), dim3(LOG_THREADS), 0, stream, log,
+    hipLaunchKernelGGL(k_episode_log_harvest, dim3(1 + log_blocks(B)), dim3(LOG_THREADS), 0, stream, log,
                        out, scalars, B);
     return hipGetLastError();
 }
@@ -659,7 +657,7 @@ hipError_t launch_episode_log_harvest(const sl_episode_log &log, const sl_step_o
 hipError_t launch_episode_log_join(const sl_episode_log &log, const sl_episode_queue &queue, const double *scores,
                                    const uint16_t *keys, const int32_t *n_cells, const sl_log_weights &weights,
                                    hipStream_t stream) {
-    hipLaunchKernelGGL(k_episode_log_join, dim3((queue.capacity + LOG_THREADS - 1) / LOG_THREADS), dim3(LOG_THREADS), 0,
+    hipLaunchKernelGGL(k_episode_log_join, dim3(log_blocks(queue.capacity)), dim3(LOG_THREADS), 0,
                        stream, log, queue, scores, keys, n_cells, weights);
     return hipGetLastError();
 }

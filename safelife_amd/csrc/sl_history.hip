@@ -118,11 +118,7 @@ __global__ __launch_bounds__(HIST_THREADS) void k_history_book(sl_episode_histor
             __syncthreads();
             const int lo = tid * HIST_PER_LANE;
             unsigned long long m = 0;                           // bit i: env tile + lo + i is done
-            if (lo < nt) {
-#pragma unroll
-                for (int k = 0; k < HIST_PER_LANE / 4; ++k)     // bytes b0 b1 b2 b3 of a word -> bits 24..27 of the product
-                    m |= (unsigned long long)((flags[lo / 4 + k] * 0x01020408u >> 24) & 0xFu) << (4 * k);
-            }
+            if (lo < nt) { SL_FLAG_BYTES_TO_MASK(m, flags, lo, HIST_PER_LANE); }
             int n_tile = 0;
             const int place = block_exclusive_scan<HIST_THREADS>(__popcll(m), wave_sum, n_tile);
             lane_mask[tid] = m;

@@ -163,18 +163,6 @@ __device__ __forceinline__ double sum_in_order(const double *lds, int m, W w) {
     return sum;
 }
 
-// has env e finished: its record's done flag; with A agents, all A of them (the step on which the env reloads)
-template <bool MULTI>
-__device__ __forceinline__ bool env_done(const sl_step_out *__restrict__ out, int e, int A) {
-    if (!MULTI) return out[e].done != 0;
-    const sl_step_out *rec = out + (long long)e * A;
-    bool d = true;
-#pragma unroll
-    for (int a = 0; a < SL_MAX_AGENTS; ++a)             // (independent loads)
-        if (a < A) d &= rec[a].done != 0;
-    return d;
-}
-
 // np.average(reward / reward_possible) over the env's A agents (env_factory.py:95): float64 quotients, np.add.reduce -- the
 // identity 0.0 plus the sum in index order for fewer than 8 elements, plus numpy's eight-accumulator tree for exactly 8 --
 // divided by A once
@@ -223,11 +211,7 @@ __device__ __forceinline__ void harvest(const sl_level_schedule &s, const int32_
         __syncthreads();
         const int lo = threadIdx.x * HARVEST_PER_LANE;
         unsigned long long mask = 0;                    // bit i: env tile + lo + i is done
-        if (lo < nt) {
-#pragma unroll
-            for (int k = 0; k < HARVEST_PER_LANE / 4; ++k)      // bytes b0 b1 b2 b3 of a word -> bits 24..27 of the product
-                mask |= (unsigned long long)((flags[lo / 4 + k] * 0x01020408u >> 24) & 0xFu) << (4 * k);
-        }
+        if (lo < nt) { SL_FLAG_BYTES_TO_MASK(mask, flags, lo, HARVEST_PER_LANE); }
         int cnt[MAXG], n_tile[MAXG];
 #pragma unroll
         for (int j = 0; j < MAXG; ++j) cnt[j] = 0;

@@ -36,36 +36,192 @@ ROW_DTYPE = np.dtype([("index", "<i8"), ("training_steps", "<i8"), ("prev", "<i8
                       ("reward_needed", "<i4"), ("success", "u1"), ("times_up", "u1"), ("flags", "u1"), ("reserved", "u1"),
                       ("reward_frac", "<f8"), ("side_effects", "<f8", (2,)), ("side_effects_frac", "<f8"), ("score", "<f8")])
 assert ROW_DTYPE.itemsize == 96
-_ROW_WORDS = ROW_DTYPE.itemsize // 8
 _DEFAULT_POLYAK = {"training": 0.99}
 RUN_SUMMARY_FIELDS = ("rows", "success", "avg_length", "side_effects", "reward", "score", "side_effects_std", "reward_std",
                       "score_std", "successful_length", "successful_length_std", "successes")
 
 
-def _common_arguments(num_envs, capacity, episode_type, summary_polyak, side_effect_weights):
-    """The checks both logs share -> num_envs, capacity, episode_type, summary_polyak, the weights' dict and their
-    ``struct sl_log_weights``."""
-    num_envs, capacity, episode_type = int(num_envs), int(capacity), str(episode_type)
-    if num_envs < 1:
-        raise ValueError("num_envs must be at least 1")
-    if capacity < num_envs:
-        raise ValueError("capacity (%d) must be at least num_envs (%d): one step can end every env's episode"
-                         % (capacity, num_envs))
-    p = _DEFAULT_POLYAK.get(episode_type, 1.0) if summary_polyak is None else float(summary_polyak)
-    if not (np.isfinite(p) and p >= 0.0):
-        raise ValueError("summary_polyak must be finite and not negative, got %r" % (summary_polyak,))
-    from .side_effects import name_to_cell
-    weights = dict(side_effect_weights or {})
-    if len(weights) > _hip.SL_SE_MAX_KEYS:
-        raise ValueError("at most %d side-effect weights, got %d" % (_hip.SL_SE_MAX_KEYS, len(weights)))
-    w = _hip.LogWeights()
-    w.n = len(weights)
-    for j, (name, weight) in enumerate(weights.items()):
-        w.cell[j], w.weight[j] = name_to_cell(name), float(weight)
-    return num_envs, capacity, episode_type, p, weights, w
+class _EpisodeLogBase(object):
+    """What ``EpisodeLog`` and ``MultiAgentEpisodeLog`` share: the arguments' checks, the device state, the calls of the
+    entry points and the host's views.  A subclass says what differs: ``_struct`` (its ctypes struct), ``_suffix`` (of its
+    ``slhip_episode_log_*`` entry points), ``_env_class`` (for the messages), ``n_keys`` (summary chains), ``row_dtype``,
+    ``available`` (int32 [L] or [L, A]; ``cur_required`` is [B] or [B, A] with it), ``_check_agents()``,
+    ``_extra_state()``, ``_now()``, ``harvest()`` (the call of every step: no layer under it) with ``_after_step()``,
+    ``summary()`` and ``records()``."""
+
+    def __init__(self, pool, num_envs, capacity, episode_type, summary_polyak, side_effect_weights):
+        if not isinstance(pool, LevelPool):
+            raise TypeError("pool must be a LevelPool")
+        self._check_agents(int(pool.n_agents))
+        self.pool = pool
+        num_envs, capacity, episode_type = int(num_envs), int(capacity), str(episode_type)
+        if num_envs < 1:
+            raise ValueError("num_envs must be at least 1")
+        if capacity < num_envs:
+            raise ValueError("capacity (%d) must be at least num_envs (%d): one step can end every env's episode"
+                             % (capacity, num_envs))
+        p = _DEFAULT_POLYAK.get(episode_type, 1.0) if summary_polyak is None else float(summary_polyak)
+        if not (np.isfinite(p) and p >= 0.0):
+            raise ValueError("summary_polyak must be finite and not negative, got %r" % (summary_polyak,))
+        from .side_effects import name_to_cell
+        weights = dict(side_effect_weights or {})
+        if len(weights) > _hip.SL_SE_MAX_KEYS:
+            raise ValueError("at most %d side-effect weights, got %d" % (_hip.SL_SE_MAX_KEYS, len(weights)))
+        w = self._weights = _hip.LogWeights()
+        w.n = len(weights)
+        for j, (name, weight) in enumerate(weights.items()):
+            w.cell[j], w.weight[j] = name_to_cell(name), float(weight)
+        self.num_envs, self.capacity, self.episode_type, self.summary_polyak = num_envs, capacity, episode_type, p
+        self.side_effect_weights = weights
+        self.env = None
+        self.t = None
+
+    def _extra_state(self):
+        """-> {struct field: int} and {struct field: numpy array, which becomes a device tensor of that name} beyond
+        ``sl_episode_log``'s."""
+        return {}, {}
+
+    def reward_possible(self, points_on_level_exit=1):
+        """What the logger records as ``reward_possible`` (:286-287), int32 of ``available``'s shape."""
+        return (self.available.astype(np.int64) + int(points_on_level_exit)).astype(np.int32)
+
+    # ---- device side
+
+    def allocate(self, torch, device, points_on_level_exit=1):
+        """The device state (the env calls this through ``_attach``; a caller with step records of its own calls it and
+        ``harvest()`` itself)."""
+        B, cap, dev, n = self.num_envs, self.capacity, device, self.n_keys
+        fields, arrays = self._extra_state()
+        self.torch = torch
+        t = self.t = {}
+        t["rows"] = torch.zeros((cap, self.row_dtype.itemsize // 8), dtype=torch.int64, device=dev)
+        t["rows"][:, 0] = -1                        # (no row's index)
+        # counters | counts | values | weights in one buffer: summary() is one host visit
+        t["state"] = torch.zeros(5 + 3 * n, dtype=torch.int64, device=dev)
+        t["counters"], t["count"] = t["state"][0:5], t["state"][5:5 + n]
+        t["value"] = t["state"][5 + n:5 + 2 * n].view(torch.float64)
+        t["weight"] = t["state"][5 + 2 * n:].view(torch.float64)
+        t["cur_slot"] = torch.zeros(B, dtype=torch.int32, device=dev)
+        t["cur_required"] = torch.zeros((B,) + self.available.shape[1:], dtype=torch.int32, device=dev)
+        t["cur_episode"] = torch.zeros(B, dtype=torch.int32, device=dev)
+        t["last_row"] = torch.full((B,), -1, dtype=torch.int64, device=dev)
+        t["reward_possible"] = torch.from_numpy(self.reward_possible(points_on_level_exit)).to(dev)
+        for name, array in arrays.items():
+            t[name] = torch.from_numpy(array).to(dev)
+        t["run_summary"] = torch.zeros(_hip.LOG_RUN_SUMMARY, dtype=torch.float64, device=dev)
+        s = self.struct = self._struct()
+        s.capacity, s.B, s.L, s.polyak = cap, B, self.pool.n_slots, self.summary_polyak
+        for name, value in fields.items():
+            setattr(s, name, value)
+        for name in ("rows", "counters", "cur_slot", "cur_required", "cur_episode", "last_row", "reward_possible", "value",
+                     "count", "weight") + tuple(arrays):
+            setattr(s, name, t[name].data_ptr())
+        self._sref = C.byref(s)
+        self._lib = _hip.lib()
+        self._harvest_entry, self._join_entry, self._summaries_entry, self._run_summary_entry = (
+            getattr(self._lib, "slhip_episode_log_" + name + self._suffix)
+            for name in ("harvest", "join", "summaries", "run_summary"))
+        return t
+
+    def _attach(self, env):
+        if self.env is not None:
+            raise ValueError("this %s already serves an env" % type(self).__name__)
+        if env.pool is not self.pool:
+            raise ValueError("the episode log was built for another pool")
+        if env.num_envs != self.num_envs:
+            raise ValueError("the episode log was built for %d envs, the env has %d" % (self.num_envs, env.num_envs))
+        self.allocate(env.torch, env.device, getattr(env, "base", env).struct.exit_points)
+        self.env = env
+        self._rewind()
+
+    def _rewind(self, mask=None):
+        """After the envs (those with mask != 0) have been reset from outside the step: their episodes start over."""
+        t, torch = self.t, self.torch
+        for name, value in self._now().items():
+            sel = None if mask is None else (mask != 0 if value.dim() == 1 else (mask != 0)[:, None])
+            t[name].copy_(value if sel is None else torch.where(sel, value, t[name]))
+        if mask is None:
+            t["last_row"].fill_(-1)
+        else:
+            t["last_row"].masked_fill_(mask != 0, -1)
+
+    def join(self, count, records, scores, keys, n_cells):
+        """The join of one flushed queue (device tensors: count int32 [1], records int32 [C,8], scores float64 [C,K,2], keys
+        [C,K] 16-bit, n_cells int32 [C,K]; one entry per env episode) on the current stream."""
+        q = _hip.EpisodeQueue()
+        q.capacity, q.env_base = int(records.shape[0]), 0
+        q.count, q.records = count.data_ptr(), records.data_ptr()
+        _hip.check(self._join_entry(self._sref, C.byref(q), _hip.ptr(scores), _hip.ptr(keys), _hip.ptr(n_cells),
+                                       C.byref(self._weights), _hip.current_stream_ptr()))
+
+    def summarise(self):
+        """Folds the rows not yet consumed into the running summaries, on the current stream."""
+        _hip.check(self._summaries_entry(self._sref, _hip.current_stream_ptr()))
+
+    def flush(self):
+        """On the caller's stream: with a side-effect queue on the env, ``side_effects_flush()``, ``scores_all()`` and the
+        join; then the summaries.  Returns the ``SideEffectBatch`` or None.  Without a queue ``side_effects`` and ``score``
+        simply never count."""
+        env, batch = self.env, None
+        if env is None:
+            raise ValueError("the episode log is not attached to an env")
+        if getattr(env, "base", env)._se is not None:
+            batch = env.side_effects_flush()
+            emd = batch.scores_all()
+            self.join(batch.count, batch.rec_tensor, emd["scores"], batch.keys, emd["n_cells"])
+        self.summarise()
+        return batch
+
+    def reset_summary(self):
+        """``SafeLifeLogger.reset_summary()`` (safelife_logger.py:406-414): the running summaries start over --
+        ``summary_stats``, ``summary_counts`` and the weights the next values meet go to zero, on the caller's stream.  Rows
+        and counters stay; rows not yet summarised are still folded in by the next ``flush()``."""
+        self._device_state()[5:].zero_()
+
+    # ---- host side: each of these is one visit
+
+    def _device_state(self):
+        if self.t is None:
+            raise ValueError("the episode log has no device state yet: hand it to %s(episode_log=...)" % self._env_class)
+        return self.t["state"]
+
+    def _state(self):
+        raw, n = self._device_state().cpu().numpy(), self.n_keys
+        return (dict(zip(_hip.LOG_COUNTERS, raw[0:5].tolist())), raw[5:5 + n].copy(),
+                raw[5 + n:5 + 2 * n].copy().view(np.float64), raw[5 + 2 * n:].copy().view(np.float64))
+
+    def counters(self):
+        """``n_rows``, ``steps``, ``episodes``, ``summarised``, ``unmatched``."""
+        return self._state()[0]
+
+    def rows(self, first=None):
+        """The rows [max(first, n_rows - capacity), n_rows) in row order: a numpy record array of ``self.row_dtype``
+        (``ROW_DTYPE``, or ``multi_row_dtype(A)``: the header's fields and ``agents`` [A])."""
+        n_rows = self.counters()["n_rows"]
+        lo = max(0 if first is None else int(first), n_rows - self.capacity, 0)
+        ring = self.t["rows"].cpu().numpy().view(self.row_dtype).reshape(-1)
+        return ring[np.arange(lo, max(n_rows, lo)) % self.capacity]
+
+    def _level_names(self, level_names):
+        if level_names is None:
+            level_names = [getattr(lv, "name", None) or "level-%d" % k for k, lv in enumerate(self.pool.levels)]
+        return level_names
+
+    def run_summary(self, first_row=0):
+        """``summarize_run_file`` over the rows [max(first_row, n_rows - capacity), n_rows): its five means (``success``,
+        ``avg_length``, ``side_effects``, ``reward``, ``score``), the printed standard deviations, the successful length
+        and the row count.  With several agents ``success``, ``avg_length``, ``reward``, ``score`` and the successful
+        length are over all rows x agents entries and ``side_effects`` over the rows; ``rows`` is the number of rows,
+        ``successes`` of successful entries."""
+        out = self.t["run_summary"]
+        _hip.check(self._run_summary_entry(self._sref, int(first_row), _hip.ptr(out), _hip.current_stream_ptr()))
+        vals = out.cpu().numpy()
+        res = dict(zip(RUN_SUMMARY_FIELDS, vals.tolist()))
+        res["rows"], res["successes"] = int(vals[0]), int(vals[11])
+        return res
 
 
-class EpisodeLog(object):
+class EpisodeLog(_EpisodeLogBase):
     """
     pool : LevelPool            single-agent
     num_envs : int              of the env it will serve
@@ -80,137 +236,37 @@ class EpisodeLog(object):
     drive it.  ``reset(mask)`` forgets the reset envs' row chains: flush before it, or the queue entries of those envs count
     as ``unmatched``.
     """
+    _struct, _suffix, _env_class = _hip.EpisodeLog, "", "SafeLifeVectorEnv"
+    n_keys = len(_hip.LOG_KEYS)
+    row_dtype = ROW_DTYPE
 
     def __init__(self, pool, num_envs, capacity, episode_type="training", summary_polyak=None, side_effect_weights=None):
-        if not isinstance(pool, LevelPool):
-            raise TypeError("pool must be a LevelPool")
-        if int(pool.n_agents) > 1:
-            raise ValueError("the episode log serves a single-agent SafeLifeVectorEnv: this pool has %d agents per level "
-                             "(MultiAgentEpisodeLog serves a SafeLifeMultiAgentVectorEnv)" % pool.n_agents)
-        self.pool = pool
-        (self.num_envs, self.capacity, self.episode_type, self.summary_polyak, self.side_effect_weights,
-         self._weights) = _common_arguments(num_envs, capacity, episode_type, summary_polyak, side_effect_weights)
+        super(EpisodeLog, self).__init__(pool, num_envs, capacity, episode_type, summary_polyak, side_effect_weights)
         # per slot: agent 0's available points (safelife_game.py:696-709), as LevelSchedule computes them
         self.available = np.zeros(pool.n_slots, np.int32)
         for k, lv in enumerate(pool.levels):
             table = pool.points_table[pool.pool_table_idx[k]].astype(np.int64)
             self.available[k] = available_points(table, pool.initial_counts[k], initial_colors(lv.board))
-        self.env = None
-        self.t = None
 
-    def reward_possible(self, points_on_level_exit=1):
-        """What the logger records as ``reward_possible`` (:286-287), int32 [L]."""
-        return (self.available.astype(np.int64) + int(points_on_level_exit)).astype(np.int32)
+    def _check_agents(self, A):
+        if A > 1:
+            raise ValueError("the episode log serves a single-agent SafeLifeVectorEnv: this pool has %d agents per level "
+                             "(MultiAgentEpisodeLog serves a SafeLifeMultiAgentVectorEnv)" % A)
 
-    # ---- device side
-
-    def allocate(self, torch, device, points_on_level_exit=1):
-        """The device state (``SafeLifeVectorEnv`` calls this through ``_attach``; a caller with step records of its own
-        calls it and ``harvest()`` itself)."""
-        B, cap, dev = self.num_envs, self.capacity, device
-        self.torch = torch
-        t = self.t = {}
-        t["rows"] = torch.zeros((cap, _ROW_WORDS), dtype=torch.int64, device=dev)
-        t["rows"][:, 0] = -1                        # (no row's index)
-        # counters | counts | values | weights in one buffer: summary() is one host visit
-        t["state"] = torch.zeros(20, dtype=torch.int64, device=dev)
-        t["counters"], t["count"] = t["state"][0:5], t["state"][5:10]
-        t["value"], t["weight"] = t["state"][10:15].view(torch.float64), t["state"][15:20].view(torch.float64)
-        t["cur_slot"] = torch.zeros(B, dtype=torch.int32, device=dev)
-        t["cur_required"] = torch.zeros(B, dtype=torch.int32, device=dev)
-        t["cur_episode"] = torch.zeros(B, dtype=torch.int32, device=dev)
-        t["last_row"] = torch.full((B,), -1, dtype=torch.int64, device=dev)
-        t["reward_possible"] = torch.from_numpy(self.reward_possible(points_on_level_exit)).to(dev)
-        t["run_summary"] = torch.zeros(_hip.LOG_RUN_SUMMARY, dtype=torch.float64, device=dev)
-        s = self.struct = _hip.EpisodeLog()
-        s.capacity, s.B, s.L, s.polyak = cap, B, self.pool.n_slots, self.summary_polyak
-        for name in ("rows", "counters", "cur_slot", "cur_required", "cur_episode", "last_row", "reward_possible", "value",
-                     "count", "weight"):
-            setattr(s, name, t[name].data_ptr())
-        self._sref = C.byref(s)
-        self._lib = _hip.lib()
-        return t
-
-    def _attach(self, env):
-        if self.env is not None:
-            raise ValueError("this EpisodeLog already serves an env")
-        if env.pool is not self.pool:
-            raise ValueError("the episode log was built for another pool")
-        if env.num_envs != self.num_envs:
-            raise ValueError("the episode log was built for %d envs, the env has %d" % (self.num_envs, env.num_envs))
-        self.allocate(env.torch, env.device, env.struct.exit_points)
-        self.env = env
-        self._rewind()
-
-    def _rewind(self, mask=None):
-        """After the envs (those with mask != 0) have been reset from outside the step: their episodes start over."""
-        sc, cols, t, torch = self.env.t["scalars"], _hip.SCALAR_COLS, self.t, self.torch
-        for name, col in (("cur_slot", "level_idx"), ("cur_required", "required_points"), ("cur_episode", "episode_idx")):
-            now = sc[:, cols[col]]
-            t[name].copy_(now if mask is None else torch.where(mask != 0, now, t[name]))
-        if mask is None:
-            t["last_row"].fill_(-1)
-        else:
-            t["last_row"].masked_fill_(mask != 0, -1)
+    def _now(self):
+        sc, cols = self.env.t["scalars"], _hip.SCALAR_COLS
+        return {"cur_slot": sc[:, cols["level_idx"]], "cur_required": sc[:, cols["required_points"]],
+                "cur_episode": sc[:, cols["episode_idx"]]}
 
     def harvest(self, out, scalars):
         """One launch on the current stream: rows for the envs whose record in `out` (int32 [B,4], ``struct sl_step_out``)
         says done; `scalars` int32 [B,16] as the step left them."""
-        rc = self._lib.slhip_episode_log_harvest(self._sref, _hip.ptr(out), _hip.ptr(scalars), self.num_envs,
-                                                 _hip.current_stream_ptr())
+        rc = self._harvest_entry(self._sref, _hip.ptr(out), _hip.ptr(scalars), self.num_envs, _hip.current_stream_ptr())
         if rc:
             _hip.check(rc)
 
     def _after_step(self):
         self.harvest(self.env.t["out"], self.env.t["scalars"])
-
-    def join(self, count, records, scores, keys, n_cells):
-        """The join of one flushed queue (device tensors: count int32 [1], records int32 [C,8], scores float64 [C,K,2], keys
-        [C,K] 16-bit, n_cells int32 [C,K]) on the current stream."""
-        q = _hip.EpisodeQueue()
-        q.capacity, q.env_base = int(records.shape[0]), 0
-        q.count, q.records = count.data_ptr(), records.data_ptr()
-        _hip.check(self._lib.slhip_episode_log_join(self._sref, C.byref(q), _hip.ptr(scores), _hip.ptr(keys), _hip.ptr(n_cells),
-                                                    C.byref(self._weights), _hip.current_stream_ptr()))
-
-    def summarise(self):
-        """Folds the rows not yet consumed into the running summaries, on the current stream."""
-        _hip.check(self._lib.slhip_episode_log_summaries(self._sref, _hip.current_stream_ptr()))
-
-    def flush(self):
-        """On the caller's stream: with a side-effect queue on the env, ``side_effects_flush()``, ``scores_all()`` and the
-        join; then the summaries.  Returns the ``SideEffectBatch`` or None.  Without a queue ``side_effects`` and ``score``
-        simply never count."""
-        env, batch = self.env, None
-        if env is None:
-            raise ValueError("the episode log is not attached to an env")
-        if env._se is not None:
-            batch = env.side_effects_flush()
-            emd = batch.scores_all()
-            self.join(batch.count, batch.rec_tensor, emd["scores"], batch.keys, emd["n_cells"])
-        self.summarise()
-        return batch
-
-    def reset_summary(self):
-        """``SafeLifeLogger.reset_summary()`` (safelife_logger.py:406-414): the running summaries start over --
-        ``summary_stats``, ``summary_counts`` and the weights the next values meet go to zero, on the caller's stream.  Rows
-        and counters stay; rows not yet summarised are still folded in by the next ``flush()``."""
-        if self.t is None:
-            raise ValueError("the episode log has no device state yet: hand it to SafeLifeVectorEnv(episode_log=...)")
-        self.t["state"][5:].zero_()
-
-    # ---- host side: each of these is one visit
-
-    def _state(self):
-        if self.t is None:
-            raise ValueError("the episode log has no device state yet: hand it to SafeLifeVectorEnv(episode_log=...)")
-        raw = self.t["state"].cpu().numpy()
-        return (dict(zip(_hip.LOG_COUNTERS, raw[0:5].tolist())), raw[5:10].copy(), raw[10:15].copy().view(np.float64),
-                raw[15:20].copy().view(np.float64))
-
-    def counters(self):
-        """``n_rows``, ``steps``, ``episodes``, ``summarised``, ``unmatched``."""
-        return self._state()[0]
 
     def summary(self):
         """``{"training/length": ..., ...}`` for the keys that have met a finite value, plus ``training/steps`` and
@@ -221,31 +277,10 @@ class EpisodeLog(object):
         out[tag + "/steps"], out[tag + "/episodes"] = counters["steps"], counters["episodes"]
         return out
 
-    def rows(self, first=None):
-        """The rows [max(first, n_rows - capacity), n_rows) in row order: a numpy record array of ``ROW_DTYPE``."""
-        n_rows = self.counters()["n_rows"]
-        lo = max(0 if first is None else int(first), n_rows - self.capacity, 0)
-        ring = self.t["rows"].cpu().numpy().view(ROW_DTYPE).reshape(-1)
-        return ring[np.arange(lo, max(n_rows, lo)) % self.capacity]
-
     def records(self, level_names=None, first=None):
         """The rows as the reference's ``log_data`` dicts (:282-302) without ``time``, for whoever writes the JSON log.
         ``level_names``: one title per pool slot (default: the pool's levels' names, where they have one)."""
-        if level_names is None:
-            level_names = [getattr(lv, "name", None) or "level-%d" % k for k, lv in enumerate(self.pool.levels)]
-        return rows_to_records(self.rows(first), level_names)
-
-    def run_summary(self, first_row=0):
-        """``summarize_run_file`` over the rows [max(first_row, n_rows - capacity), n_rows): its five means (``success``,
-        ``avg_length``, ``side_effects``, ``reward``, ``score``), the printed standard deviations, the successful length
-        and the row count."""
-        out = self.t["run_summary"]
-        _hip.check(self._lib.slhip_episode_log_run_summary(self._sref, int(first_row), _hip.ptr(out),
-                                                           _hip.current_stream_ptr()))
-        vals = out.cpu().numpy()
-        res = dict(zip(RUN_SUMMARY_FIELDS, vals.tolist()))
-        res["rows"], res["successes"] = int(vals[0]), int(vals[11])
-        return res
+        return rows_to_records(self.rows(first), self._level_names(level_names))
 
 
 def multi_row_dtype(n_agents):
@@ -261,7 +296,7 @@ def multi_row_dtype(n_agents):
     return row
 
 
-class MultiAgentEpisodeLog(object):
+class MultiAgentEpisodeLog(_EpisodeLogBase):
     """
     The episode log for a ``SafeLifeMultiAgentVectorEnv``: what ``SafeLifeLogger`` does when ``info['episode']`` holds
     arrays over the agents (safelife_logger.py:289-291, :319-328).  A row per env EPISODE, filed on the step where all its
@@ -279,18 +314,14 @@ class MultiAgentEpisodeLog(object):
     Attach with ``SafeLifeMultiAgentVectorEnv(pool, ..., episode_log=log)`` (``auto_reset=True``); the surface is
     ``EpisodeLog``'s.
     """
+    _struct, _suffix, _env_class = _hip.EpisodeLogMulti, "_multi", "SafeLifeMultiAgentVectorEnv"
+    n_keys = _hip.LOG_MAX_NAMES * len(_hip.LOG_MULTI_KEYS)
 
     def __init__(self, pool, num_envs, capacity, episode_type="training", summary_polyak=None, side_effect_weights=None,
                  agent_names=None):
-        if not isinstance(pool, LevelPool):
-            raise TypeError("pool must be a LevelPool")
-        A = self.n_agents = int(pool.n_agents)
-        if not 1 <= A <= _hip.SL_MAX_AGENTS:
-            raise ValueError("the pool must have 1 to %d agents per level, not %d" % (_hip.SL_MAX_AGENTS, A))
-        self.pool = pool
-        (self.num_envs, self.capacity, self.episode_type, self.summary_polyak, self.side_effect_weights,
-         self._weights) = _common_arguments(num_envs, capacity, episode_type, summary_polyak, side_effect_weights)
-        L = pool.n_slots
+        super(MultiAgentEpisodeLog, self).__init__(pool, num_envs, capacity, episode_type, summary_polyak,
+                                                   side_effect_weights)
+        A, L = self.n_agents, pool.n_slots
         if agent_names is None:
             agent_names = [["agent%d" % a for a in range(A)]] * L
         agent_names = [[str(n) for n in names] for names in agent_names]
@@ -314,129 +345,30 @@ class MultiAgentEpisodeLog(object):
                 idx = pool.pool_agent_table_idx[k, a] if A > 1 else pool.pool_table_idx[k]
                 self.available[k, a] = available_points(pool.points_table[idx].astype(np.int64), pool.initial_counts[k], colors)
         self.row_dtype = multi_row_dtype(A)
-        self.env = None
-        self.t = None
 
-    def reward_possible(self, points_on_level_exit=1):
-        """What the logger records as ``reward_possible`` (:286-287), int32 [L, A]."""
-        return (self.available.astype(np.int64) + int(points_on_level_exit)).astype(np.int32)
+    def _check_agents(self, A):
+        self.n_agents = A
+        if not 1 <= A <= _hip.SL_MAX_AGENTS:
+            raise ValueError("the pool must have 1 to %d agents per level, not %d" % (_hip.SL_MAX_AGENTS, A))
 
-    # ---- device side
+    def _extra_state(self):
+        return {"n_agents": self.n_agents, "n_names": len(self.names)}, {"name_id": self.name_id}
 
-    def allocate(self, torch, device, points_on_level_exit=1):
-        """The device state (``SafeLifeMultiAgentVectorEnv`` calls this through ``_attach``; a caller with step records of
-        its own calls it and ``harvest()`` itself)."""
-        B, A, cap, dev = self.num_envs, self.n_agents, self.capacity, device
-        n_keys = _hip.LOG_MAX_NAMES * len(_hip.LOG_MULTI_KEYS)
-        self.torch = torch
-        t = self.t = {}
-        t["rows"] = torch.zeros((cap, self.row_dtype.itemsize // 8), dtype=torch.int64, device=dev)
-        t["rows"][:, 0] = -1                        # (no row's index)
-        # counters | counts | values | weights in one buffer: summary() is one host visit
-        t["state"] = torch.zeros(5 + 3 * n_keys, dtype=torch.int64, device=dev)
-        t["counters"], t["count"] = t["state"][0:5], t["state"][5:5 + n_keys]
-        t["value"] = t["state"][5 + n_keys:5 + 2 * n_keys].view(torch.float64)
-        t["weight"] = t["state"][5 + 2 * n_keys:].view(torch.float64)
-        t["cur_slot"] = torch.zeros(B, dtype=torch.int32, device=dev)
-        t["cur_required"] = torch.zeros((B, A), dtype=torch.int32, device=dev)
-        t["cur_episode"] = torch.zeros(B, dtype=torch.int32, device=dev)
-        t["last_row"] = torch.full((B,), -1, dtype=torch.int64, device=dev)
-        t["reward_possible"] = torch.from_numpy(self.reward_possible(points_on_level_exit)).to(dev)
-        t["name_id"] = torch.from_numpy(self.name_id).to(dev)
-        t["run_summary"] = torch.zeros(_hip.LOG_RUN_SUMMARY, dtype=torch.float64, device=dev)
-        s = self.struct = _hip.EpisodeLogMulti()
-        s.capacity, s.B, s.L, s.n_agents, s.n_names, s.polyak = cap, B, self.pool.n_slots, A, len(self.names), self.summary_polyak
-        for name in ("rows", "counters", "cur_slot", "cur_required", "cur_episode", "last_row", "reward_possible", "name_id",
-                     "value", "count", "weight"):
-            setattr(s, name, t[name].data_ptr())
-        self._sref = C.byref(s)
-        self._lib = _hip.lib()
-        return t
-
-    def _attach(self, env):
-        if self.env is not None:
-            raise ValueError("this MultiAgentEpisodeLog already serves an env")
-        if env.pool is not self.pool:
-            raise ValueError("the episode log was built for another pool")
-        if env.num_envs != self.num_envs:
-            raise ValueError("the episode log was built for %d envs, the env has %d" % (self.num_envs, env.num_envs))
-        self.allocate(env.torch, env.device, env.base.struct.exit_points)
-        self.env = env
-        self._rewind()
-
-    def _rewind(self, mask=None):
-        """After the envs (those with mask != 0) have been reset from outside the step: their episodes start over."""
-        env, cols, t, torch = self.env, _hip.SCALAR_COLS, self.t, self.torch
-        sc = env.base.t["scalars"]
-        now = {"cur_slot": sc[:, cols["level_idx"]], "cur_episode": sc[:, cols["episode_idx"]],
-               "cur_required": env.t["agents"][:, :, _hip.AGENT_COLS["required_points"]]}
-        for name, value in now.items():
-            sel = None if mask is None else (mask != 0 if value.dim() == 1 else (mask != 0)[:, None])
-            t[name].copy_(value if sel is None else torch.where(sel, value, t[name]))
-        if mask is None:
-            t["last_row"].fill_(-1)
-        else:
-            t["last_row"].masked_fill_(mask != 0, -1)
+    def _now(self):
+        sc, cols = self.env.base.t["scalars"], _hip.SCALAR_COLS
+        return {"cur_slot": sc[:, cols["level_idx"]], "cur_episode": sc[:, cols["episode_idx"]],
+                "cur_required": self.env.t["agents"][:, :, _hip.AGENT_COLS["required_points"]]}
 
     def harvest(self, out, agents, scalars):
         """One launch on the current stream: rows for the envs ALL of whose records in `out` (int32 [B,A,4], ``struct
         sl_step_out``) say done; `agents` int32 [B,A,12] and `scalars` int32 [B,16] as the step left them."""
-        rc = self._lib.slhip_episode_log_harvest_multi(self._sref, _hip.ptr(out), _hip.ptr(agents), _hip.ptr(scalars),
-                                                       self.num_envs, _hip.current_stream_ptr())
+        rc = self._harvest_entry(self._sref, _hip.ptr(out), _hip.ptr(agents), _hip.ptr(scalars), self.num_envs,
+                                 _hip.current_stream_ptr())
         if rc:
             _hip.check(rc)
 
     def _after_step(self):
         self.harvest(self.env.t["out"], self.env.t["agents"], self.env.base.t["scalars"])
-
-    def join(self, count, records, scores, keys, n_cells):
-        """The join of one flushed queue (one entry per env episode; the tensors of ``EpisodeLog.join``)."""
-        q = _hip.EpisodeQueue()
-        q.capacity, q.env_base = int(records.shape[0]), 0
-        q.count, q.records = count.data_ptr(), records.data_ptr()
-        _hip.check(self._lib.slhip_episode_log_join_multi(self._sref, C.byref(q), _hip.ptr(scores), _hip.ptr(keys),
-                                                          _hip.ptr(n_cells), C.byref(self._weights),
-                                                          _hip.current_stream_ptr()))
-
-    def summarise(self):
-        """Folds the rows not yet consumed into the running summaries, on the current stream."""
-        _hip.check(self._lib.slhip_episode_log_summaries_multi(self._sref, _hip.current_stream_ptr()))
-
-    def flush(self):
-        """On the caller's stream: with a side-effect queue on the env, its ``side_effects_flush()``, ``scores_all()`` and
-        the join; then the summaries.  Returns the ``SideEffectBatch`` or None.  Without a queue the scores never count."""
-        env, batch = self.env, None
-        if env is None:
-            raise ValueError("the episode log is not attached to an env")
-        if env.base._se is not None:
-            batch = env.side_effects_flush()
-            emd = batch.scores_all()
-            self.join(batch.count, batch.rec_tensor, emd["scores"], batch.keys, emd["n_cells"])
-        self.summarise()
-        return batch
-
-    def reset_summary(self):
-        """``SafeLifeLogger.reset_summary()``, as ``EpisodeLog.reset_summary``: every name's summaries start over; rows and
-        counters stay."""
-        if self.t is None:
-            raise ValueError("the episode log has no device state yet: hand it to "
-                             "SafeLifeMultiAgentVectorEnv(episode_log=...)")
-        self.t["state"][5:].zero_()
-
-    # ---- host side: each of these is one visit
-
-    def _state(self):
-        if self.t is None:
-            raise ValueError("the episode log has no device state yet: hand it to "
-                             "SafeLifeMultiAgentVectorEnv(episode_log=...)")
-        raw = self.t["state"].cpu().numpy()
-        n = _hip.LOG_MAX_NAMES * len(_hip.LOG_MULTI_KEYS)
-        return (dict(zip(_hip.LOG_COUNTERS, raw[0:5].tolist())), raw[5:5 + n].copy(),
-                raw[5 + n:5 + 2 * n].copy().view(np.float64), raw[5 + 2 * n:].copy().view(np.float64))
-
-    def counters(self):
-        """``n_rows``, ``steps``, ``episodes``, ``summarised``, ``unmatched``."""
-        return self._state()[0]
 
     def summary(self):
         """``{"training/agent0-length": ..., ...}`` for the keys that have met a finite value, name by name in the order
@@ -451,32 +383,10 @@ class MultiAgentEpisodeLog(object):
         out[tag + "/steps"], out[tag + "/episodes"] = counters["steps"], counters["episodes"]
         return out
 
-    def rows(self, first=None):
-        """The rows [max(first, n_rows - capacity), n_rows) in row order: a numpy record array of ``self.row_dtype``
-        (``multi_row_dtype(A)``: the header's fields and ``agents`` [A])."""
-        n_rows = self.counters()["n_rows"]
-        lo = max(0 if first is None else int(first), n_rows - self.capacity, 0)
-        ring = self.t["rows"].cpu().numpy().view(self.row_dtype).reshape(-1)
-        return ring[np.arange(lo, max(n_rows, lo)) % self.capacity]
-
     def records(self, level_names=None, first=None):
         """The rows as the reference's ``log_data`` dicts (:282-302) without ``time``: lists over the agents, and the
         ``agents`` key with their names."""
-        if level_names is None:
-            level_names = [getattr(lv, "name", None) or "level-%d" % k for k, lv in enumerate(self.pool.levels)]
-        return multi_rows_to_records(self.rows(first), level_names, self.names)
-
-    def run_summary(self, first_row=0):
-        """``summarize_run_file`` over the rows [max(first_row, n_rows - capacity), n_rows): ``success``, ``avg_length``,
-        ``reward``, ``score`` and the successful length over all rows x agents entries, ``side_effects`` over the rows;
-        ``rows`` is the number of rows, ``successes`` of successful entries."""
-        out = self.t["run_summary"]
-        _hip.check(self._lib.slhip_episode_log_run_summary_multi(self._sref, int(first_row), _hip.ptr(out),
-                                                                 _hip.current_stream_ptr()))
-        vals = out.cpu().numpy()
-        res = dict(zip(RUN_SUMMARY_FIELDS, vals.tolist()))
-        res["rows"], res["successes"] = int(vals[0]), int(vals[11])
-        return res
+        return multi_rows_to_records(self.rows(first), self._level_names(level_names), self.names)
 
 
 def multi_rows_to_records(rows, level_names, names):

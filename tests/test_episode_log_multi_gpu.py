@@ -533,6 +533,67 @@ def test_a_one_agent_pool_logs_agent0_keys():
     assert recs[0]["agents"] == ["agent0"] and isinstance(recs[0]["length"], list) and "side_effects" not in recs[0]
 
 
+@pytest.mark.parametrize("B", [1, 65])
+def test_a_one_agent_log_equals_the_single_agent_log(B):
+    """The harvest and the join are one body under both logs: an ``EpisodeLog`` and a one-agent ``MultiAgentEpisodeLog`` on
+    the same pool, allocated by hand and fed the same 6 steps (the records of the envs that go on poisoned, a slot outside
+    the pool) and one join of a scrambled queue with an entry that has no row, hold the same counters and the same rows, bit
+    for bit -- NaNs included.  B = 1: a lone lane; B = 65: a lane past a wave's edge."""
+    from safelife_amd.side_effects import name_to_cell
+    from tests import util
+    torch, dev = _torch(), _hip.device()
+    rng = np.random.default_rng(40 + B)
+    pool = util.pool_from_fixture("prune_still_25", util.oracle_counts, n=6)[0]
+    assert pool.n_agents == 1
+    L, K, weights = pool.n_slots, _hip.SL_SE_MAX_KEYS, {"life-green": 1.0, "life-red": 0.5, "crate-gray": -2.0}
+    one = episode_log.EpisodeLog(pool, B, 6 * B, side_effect_weights=weights)
+    many = episode_log.MultiAgentEpisodeLog(pool, B, 6 * B, side_effect_weights=weights)
+    one.allocate(torch, dev), many.allocate(torch, dev)
+    up = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+    for t, plan in enumerate(["none", "all", "some", "some", "all", "some"]):
+        raw, ag, sc = _random_step(rng, B, 1, L, _done_plan(rng, plan, B, 1))
+        sc[:, COLS["episode_idx"]] = t + 1
+        ag[:, 0, ACOLS["required_points"]] = sc[:, COLS["required_points"]]
+        out, agents, scalars = up(raw), up(ag), up(sc)
+        one.harvest(out.view(B, 4), scalars)
+        many.harvest(out, agents, scalars)
+    filed = one.rows()
+    entries = [(int(r["env"]), int(r["episode_idx"])) for r in filed] + [(0, 10 ** 6)]      # the last one: never logged
+    rng.shuffle(entries)
+    n = len(entries)
+    rec = np.zeros((n, 8), np.int32)
+    rec[:, 0], rec[:, 3] = [e for e, _ in entries], [k for _, k in entries]
+    cells = [name_to_cell(name) for name in weights] + [48, 16]
+    keys = np.full((n, K), 0xFFFF, np.uint16)
+    scores = np.full((n, K, 2), np.nan)
+    n_cells = np.zeros((n, K), np.int32)
+    for i in range(n):
+        if i % 5 == 0:
+            continue                                                    # an empty key list: totals 0, 0
+        slots = rng.choice(K, rng.integers(1, 9), replace=False)
+        keys[i, slots] = rng.choice(cells, len(slots))
+        scores[i, slots] = rng.random((len(slots), 2)) * 4
+        if i % 5 == 1:
+            scores[i, slots[0], rng.integers(0, 2)] = np.nan            # a NaN score contributes nothing
+        if i % 5 == 2:
+            n_cells[i, 0] = -1                                          # cut short: NaN totals
+    args = [up(a) for a in (np.array([n], np.int32), rec, scores, keys.view(np.int16), n_cells)]
+    one.join(*args), many.join(*args)
+    c = one.counters()
+    assert c == many.counters()
+    assert c["unmatched"] == 1 and c["steps"] == 6 * B and c["n_rows"] == c["episodes"] == len(filed) >= 2 * B
+    r1, rm = one.rows(), many.rows()
+    bits = lambda a: np.ascontiguousarray(a).view({4: np.uint32, 8: np.uint64}.get(a.dtype.itemsize, a.dtype))  # noqa: E731
+    assert len(r1) == len(rm) == c["n_rows"] and (rm["n_agents"] == 1).all()
+    for name in ("index", "training_steps", "prev", "env", "level", "episode_idx", "flags", "side_effects",
+                 "side_effects_frac"):
+        assert np.array_equal(bits(r1[name]), bits(rm[name])), name
+    for name in ("length", "reward", "reward_possible", "reward_needed", "success", "times_up", "reward_frac", "score"):
+        assert np.array_equal(bits(r1[name]), bits(rm["agents"][name][:, 0])), name
+    assert (r1["flags"] & _hip.LOG_JOINED).all()
+    assert B == 1 or (np.isnan(r1["score"]).any() and np.isfinite(r1["score"]).any())
+
+
 def test_without_a_log_nothing_changes():
     pool = _plain_pool()
     rng = np.random.default_rng(5)

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Is the device code of the row kernels the same as at another revision?  (the gate of a refactor of sl_rowlane.hip)
 #   tools/isa_same.sh <rev> [extra hipcc flags, e.g. -DSL_TRACE -DSL_DEV_SHAPES]
+#   UNITS="sl_episode_log sl_schedule sl_history" tools/isa_same.sh <rev>      other translation units of csrc/
 # Exports <rev> with git archive into a temporary directory, compiles the three row-kernel translation units of that
 # tree and of this one to listings with the build's flags (six hipcc side by side, a few minutes), and says per file
 # whether the listings are identical -- if not, the first kernel whose text differs.  Exit status 0: all identical.
@@ -11,7 +12,7 @@ trap 'rm -rf $TMP' EXIT
 mkdir -p $TMP/old $TMP/s
 git archive "$REV" | tar -x -C $TMP/old || exit 2
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-gpu-rdc -ffp-contract=off -mllvm -amdgpu-kernarg-preload-count=8"
-UNITS="sl_rowlane sl_rowlane_b sl_rowlane_c"
+UNITS=${UNITS:-sl_rowlane sl_rowlane_b sl_rowlane_c}
 for u in $UNITS; do                             # (from each tree's root: the listings name their source by relative path)
     (cd $TMP/old && /opt/rocm/bin/hipcc $FLAGS -S --cuda-device-only -fuse-cuid=none "$@" safelife_amd/csrc/$u.hip -o $TMP/s/$u.old.s) &
     /opt/rocm/bin/hipcc $FLAGS -S --cuda-device-only -fuse-cuid=none "$@" safelife_amd/csrc/$u.hip -o $TMP/s/$u.new.s &
