@@ -1,5 +1,6 @@
 """Constructed cases for the per-shape, per-variant matrix of the fused step (tests/test_step_matrix_gpu.py on the
-device, tests/test_step_matrix_host.py on the oracle alone).
+device, tests/test_step_matrix_host.py on the oracle alone), and for the same matrix on the size-generic kernels
+(tests/test_step_generic_gpu.py, tests/test_step_generic_host.py: rectangular boards, `Case(H, cfg, W=..., family="generic")`).
 
 Nothing here is random: a case is a function of (shape, configuration, batch) only.  A pool holds eight levels whose
 agents start on the cells where the row kernels change code path -- the four corners, both sides of the seam of the
@@ -39,6 +40,27 @@ def geometry(H, W):
     G = 64 // GL
     WS = (W + 1) // 2
     return dict(VERT=vert, GL=GL, G=G, NB=WAVES * G, WS=WS, cache=64 % (WAVES * G) == 0, lean_takes_queue=WS > 16)
+
+
+def generic_threads(HW):
+    """The workgroup size of the size-generic kernels (generic_threads of sl_generic.hip), restated: one wavefront for
+    boards of up to 256 cells, two up to 1024, else four."""
+    return 64 if HW <= 256 else 128 if HW <= 1024 else 256
+
+
+# The side-effect pass (what a flush of the finished-episode queue runs) takes boards of up to 4096 cells on the
+# size-generic kernels: the queue of a larger generic case is read as the step kernels left it, without the pass
+# (Case.queue_raw).
+GENERIC_QUEUE_MAX_CELLS = 4096
+
+
+def generic_geometry(H, W):
+    """The size-generic family: one board per workgroup (NB = 1) of generic_threads(H * W) threads, each thread a cell
+    per pass.  WS = ceil(W/2) means nothing to these kernels; it stays the place where the constructed items sit.  The
+    levels are dealt in groups of eight (`deal`), as on the 8-board workgroups of the row kernels."""
+    threads = generic_threads(H * W)
+    return dict(VERT=None, GL=None, G=None, NB=1, WS=(W + 1) // 2, cache=False, lean_takes_queue=False, threads=threads,
+                passes=-(-H * W // threads), deal=N_LEVELS)
 
 
 def goal_cache_expected(H, W, spawn):
@@ -179,19 +201,30 @@ def build_levels(H, W, tables, spawn):
 class Case(object):
     """One (shape, configuration, batch): the pool's levels, the env keywords and the scripted actions."""
 
-    def __init__(self, H, cfg, batch="main", B=None, n_steps=T_SINGLE + T_ROLLOUT + 1, queue=None):
+    def __init__(self, H, cfg, batch="main", B=None, n_steps=T_SINGLE + T_ROLLOUT + 1, queue=None, W=None, family="row",
+                 big_view=False):
+        """family: "row" (a square row-kernel shape; W is H) or "generic" (any H x W; 17 envs in the main batch, dealt in
+        groups of eight).  big_view: an "obs" case takes the raw view larger than the board whatever its tables and
+        spawners say (and keeps its queue)."""
         tables, spawn, front = cfg
-        W = H
-        self.H, self.W, self.cfg, self.batch = H, W, cfg, batch
+        assert family in ("row", "generic") and (family == "generic" or W in (None, H))
+        W = H if W is None else W
+        self.H, self.W, self.cfg, self.batch, self.family = H, W, cfg, batch, family
+        self.big_view = big_view
         self.tables, self.spawn, self.front = tables, spawn, front
-        self.geom = geometry(H, W)
-        NB = self.geom["NB"]
-        self.B = B if B is not None else (2 * NB + 1 if batch == "main" else NB - 1)
+        if family == "row":
+            self.geom = geometry(H, W)
+            NB = deal = self.geom["NB"]
+            self.B = B if B is not None else (2 * NB + 1 if batch == "main" else NB - 1)
+        else:
+            self.geom = generic_geometry(H, W)
+            deal = self.geom["deal"]
+            self.B = B if B is not None else 2 * deal + 1
         idx = CONFIGS.index(cfg)
         self.time_limit = 5 + idx % 5
         self.levels = build_levels(H, W, tables, spawn)
         e = np.arange(self.B)
-        self.first_level = ((e + e // NB) % N_LEVELS).astype(np.int32)      # (shifted by one level per workgroup)
+        self.first_level = ((e + e // deal) % N_LEVELS).astype(np.int32)    # (shifted by one level per workgroup)
         self.kw = dict(auto_reset=True, level_stride=1, time_limit=self.time_limit, view_shape=(5, 7))
         self.policy_layout, self.queue_capacity, self.reset_at = None, 0, None
         combo = (tables == "many") * 2 + (spawn == "spawn")          # 0..3: the four (table, spawn) combinations
@@ -207,6 +240,9 @@ class Case(object):
                             dict(view_shape=(5, 7), output_channels=CHANNELS_15),
                             dict(view_shape=(9, 15), output_channels=CHANNELS_15, remove_white_goals=False)][combo])
             self.policy_layout = (None, None, "uint8", "float32")[combo]
+            if big_view:
+                self.kw.update(view_shape=(H + 2, W + 1), output_channels=None)
+                self.policy_layout = None
             if combo in (1, 2) if queue is None else queue:
                 self.queue_capacity = max(2, self.B // 4)
         else:
@@ -216,7 +252,9 @@ class Case(object):
                 words[:, 3] |= np.uint64(1)                                 # a PCG64 increment is odd
                 w.update(baseline="inaction", inaction_rng=words)
             self.kw["wrappers"] = w
+        self.queue_raw = family == "generic" and H * W > GENERIC_QUEUE_MAX_CELLS
         self.wrapped = front == "wrap"
+        self.inaction = self.wrapped and spawn == "spawn"
         self.with_obs = front != "plain"
         self.n_steps = n_steps
         self.reset_mask = (np.arange(self.B) % 3 == 0).astype(np.uint8)
@@ -266,8 +304,8 @@ def all_cases():
     return [(H, cfg) for H in SHAPES for cfg in CONFIGS]
 
 
-def case_id(H, cfg):
-    return "%dx%d-%s" % (H, H, config_id(cfg))
+def case_id(H, cfg, W=None):
+    return "%dx%d-%s" % (H, H if W is None else W, config_id(cfg))
 
 
 # ---------------------------------------------------------------------------------------------- the oracle's side

@@ -717,7 +717,7 @@ def test_side_effect_pass_reproduces_reference_inputs(sp, fixture):
     from safelife_amd import _hip, side_effects as se
     from safelife_amd.levels import Level, LevelPool
     from safelife_amd.vector_env import SafeLifeVectorEnv
-    with np.load(os.path.join(util.GOLDEN, "side_effect_inputs.npz")) as d:
+    with np.load(os.path.join(util.GOLDEN, fixture)) as d:
         d = {k: d[k] for k in d.files}
     p, n_steps = float(d["spawn_prob"]), int(d["num_steps"])
     filler = Level(np.zeros_like(d["b0"]), agent_locs=np.zeros((0, 2), int))

@@ -41,9 +41,10 @@ def test_configurations_reach_every_kernel_slot(H):
         assert smc.Case(H, smc.CONFIGS[0], queue=True).slots() == smc.Case(H, smc.CONFIGS[0]).slots()
 
 
-def _pool_items(H):
+def _pool_items(H, W=None):
     """Every constructed item a pool promises, read back from its levels."""
-    W, WS = H, (H + 1) // 2
+    W = H if W is None else W
+    WS = (W + 1) // 2
     levels = smc.build_levels(H, W, "many", "spawn")
     assert len(levels) == smc.N_LEVELS
     starts = {tuple(lv.agent_locs[0]) for lv in levels if len(lv.agent_locs)}
@@ -159,7 +160,8 @@ def _run(case):
     cpu.env.reset()
     still, drew = None, np.zeros(case.B, bool)
     if case.spawn == "spawn":       # the same actions on the pool without its spawners: no draw is ever consumed there
-        twin = smc.Case(case.H, (case.tables, "still", case.front), batch=case.batch, queue=bool(case.queue_capacity))
+        twin = smc.Case(case.H, (case.tables, "still", case.front), batch=case.batch, queue=bool(case.queue_capacity),
+                        W=case.W, family=case.family, big_view=case.big_view)
         still = util.OracleBackend(twin.pool(util.oracle_counts), case.B, **case.backend_kw(device=False))
         still.env.reset()
     for t in range(case.n_steps):
@@ -180,7 +182,11 @@ def _run(case):
 def test_case_exercises_what_it_claims(H, cfg):
     case = smc.Case(H, cfg)
     assert 5 <= case.time_limit <= 9 and case.B == 2 * smc.EXPECTED_NB[H] + 1 <= 65
-    cov, drew = _run(case)
+    _assert_coverage(case, *_run(case))
+
+
+def _assert_coverage(case, cov, drew):
+    """The coverage conditions of a main-batch case (also those of the size-generic matrix, tests/test_step_generic_host.py)."""
     B, NB = case.B, case.geom["NB"]
     assert cov.crossings == {"row 0 -> H-1", "row H-1 -> 0", "col 0 -> W-1", "col W-1 -> 0"}, cov.crossings
     assert cov.stood == {0, 1}, "the agents stood on columns WS-1 and WS"

@@ -116,7 +116,8 @@ class OracleBackend(object):
         wrappers = kw.pop("wrappers", None)
         kw.pop("slices", None)
         # the product's keyword -> the oracle's: salt 1 + env_offset (0 here), or 0 = exact pool generators
-        kw["stream_salt"] = 1 + int(kw.pop("env_offset", 0)) if kw.pop("episode_streams", True) else 0
+        offset = int(kw.pop("env_offset", 0))
+        kw["stream_salt"] = 1 + offset if kw.pop("episode_streams", True) else 0
         self.env = oracle.OracleEnv(self.arrays, **kw)
         if wrappers is not None:
             self.env.set_wrappers(**wrappers)
