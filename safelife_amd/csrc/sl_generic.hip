@@ -11,6 +11,21 @@
 //   SafeLifeEnv.step     safelife/safelife_env.py:148-201 (+ safelife_game.py:505-552,684-719,746-761)
 //   SafeLifeEnv.reset    safelife/safelife_env.py:203-218
 //   SafeLifeEnv.get_obs  safelife/safelife_env.py:105-146, helper_utils.py:42-75
+//
+// The env kernels -- k_env_rollout_generic / k_env_reset_generic (one agent, state in sl_env_scalars) and
+// k_env_step_multi / k_env_reset_multi / k_multi_baseline (1-8 agents, state in sl_agent_state) -- are sequences of
+// the same phases, each defined once:
+//   block_load / block_store   board and generator words between global memory and LDS (k_env_rollout_generic keeps
+//                              its copies written out: see there)
+//   (execute_actions)          act_one by thread 0, per kernel: one agent that may be absent, or A agents in order
+//   ca_step_block, advance_goals   the CA on the board, then on the goals unless static
+//   board_score / score_agents sum(points_table * alive_counts), one table or one per agent
+//   recolor_exits[_multi]      update_exit_colors, then the step's records, by thread 0, per kernel
+//   queue_finished / copy_finished_board   the finished-episode queue
+//   flag_exit_cells, side_effect_count     SimpleSideEffectPenalty's count against a baseline the kernel names
+//   advance_level, level_to_block, reset_block[_multi], level_exits_multi      the reload of a finished env
+//   write_obs                  get_obs, once or per agent
+// and the launchers go through launch_per_board.
 #include "sl_device.h"
 #include "sl_kernels.h"
 
@@ -120,6 +135,20 @@ __device__ __forceinline__ GenericLds carve(unsigned char *smem, int HW, int nbu
 
 size_t generic_lds_bytes(int HW, int nbuf) { return 128 + (size_t)nbuf * ((HW + 7) & ~7) * sizeof(u16); }
 
+// A board and its generator's four words: global memory -> LDS at a kernel's entry, and back at its exit.  The caller
+// places the barrier.
+__device__ __forceinline__ void rng_load(const GenericLds &l, const sl_pcg64 *rng) {
+    if (threadIdx.x < 4) l.rng[threadIdx.x] = ((const u64 *)rng)[threadIdx.x];
+}
+__device__ __forceinline__ void block_load(const GenericLds &l, u16 *brd, const u16 *board, int HW, const sl_pcg64 *rng) {
+    for (int i = threadIdx.x; i < HW; i += GB) brd[i] = board[i];
+    rng_load(l, rng);
+}
+__device__ __forceinline__ void block_store(const GenericLds &l, const u16 *brd, u16 *board, int HW, sl_pcg64 *rng) {
+    for (int i = threadIdx.x; i < HW; i += GB) board[i] = brd[i];
+    if (threadIdx.x < 4) ((u64 *)rng)[threadIdx.x] = l.rng[threadIdx.x];
+}
+
 // ------------------------------------------------------------------ advance_board / occupancy
 
 // (`out` may be `in`: a board is staged into LDS in full before anything of it is stored, and no thread reads `in`
@@ -136,9 +165,7 @@ __global__ __launch_bounds__(GB_MAX) void k_advance_generic(const u16 *__restric
     if (n_valid && b >= *n_valid) return;       // only the first *n_valid boards exist (workgroup-uniform)
     if (n_each) n_steps = n_each[b];            // per-board step counts (workgroup-uniform)
     GenericLds l = carve(smem, HW, 3);
-    const u16 *src = in + (size_t)b * HW;
-    for (int i = tid; i < HW; i += GB) l.buf[0][i] = src[i];
-    if (tid < 4) l.rng[tid] = ((const u64 *)(rng + b))[tid];
+    block_load(l, l.buf[0], in + (size_t)b * HW, HW, rng + b);
     __syncthreads();
     const float inv_w = 1.0f / (float)W;
     const double p = (double)spawn_prob[b];
@@ -197,10 +224,8 @@ __global__ __launch_bounds__(GB_MAX) void k_occupancy_generic(const u16 *__restr
     if (in_run >= run_len) return;              // (workgroup-uniform, ahead of every barrier)
     GenericLds l = carve(smem, HW, 3);
     u16 *cnt = l.buf[0] + (size_t)3 * hwp;      // [8][hwp], behind the three board buffers
-    const u16 *src = in + (size_t)b * HW;
-    for (int i = tid; i < HW; i += GB) l.buf[0][i] = src[i];
+    block_load(l, l.buf[0], in + (size_t)b * HW, HW, rng + b);
     for (int i = tid; i < 4 * hwp; i += GB) ((u32 *)cnt)[i] = 0u;
-    if (tid < 4) l.rng[tid] = ((const u64 *)(rng + b))[tid];
     __syncthreads();
     const float inv_w = 1.0f / (float)W;
     const double p = (double)spawn_prob[b];
@@ -233,17 +258,14 @@ __global__ __launch_bounds__(GB_MAX) void k_occupancy_generic(const u16 *__restr
 // current board: the wrapper's reset() copies it (:168-172).
 __global__ __launch_bounds__(GB_MAX) void k_inaction_generic(sl_env_batch env, const Jump *__restrict__ jump) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int H = env.H, W = env.W, HW = H * W, b = blockIdx.x, tid = threadIdx.x;
+    const int H = env.H, W = env.W, HW = H * W, b = blockIdx.x;
     GenericLds l = carve(smem, HW, 3);
     const sl_env_scalars *sc = env.scalars + b;
     u16 *base = env.wrap.inaction_board + (size_t)b * HW;
-    const u16 *src = sc->num_steps == 0 ? env.board + (size_t)b * HW : base;
-    for (int i = tid; i < HW; i += GB) l.buf[0][i] = src[i];
-    if (tid < 4) l.rng[tid] = ((const u64 *)(env.wrap.inaction_rng + b))[tid];
+    block_load(l, l.buf[0], sc->num_steps == 0 ? env.board + (size_t)b * HW : base, HW, env.wrap.inaction_rng + b);
     __syncthreads();
     ca_step_block(l.buf[0], l.buf[1], l.buf[2], H, W, 1.0f / (float)W, (double)sc->spawn_prob, l.rng, jump, l.wave_tot);
-    for (int i = tid; i < HW; i += GB) base[i] = l.buf[2][i];
-    if (tid < 4) ((u64 *)(env.wrap.inaction_rng + b))[tid] = l.rng[tid];
+    block_store(l, l.buf[2], base, HW, env.wrap.inaction_rng + b);
 }
 
 // ------------------------------------------------------------------------------ alive_counts
@@ -397,6 +419,119 @@ __device__ void write_obs(const sl_env_batch &env, int e, const u16 *board, cons
     }
 }
 
+// ------------------------------------------------------------------------- phases of env step / reset
+// What k_env_rollout_generic (single agent) and k_env_step_multi (1-8 agents) both do, once each; every function is
+// called by all threads of the workgroup unless it says thread 0.
+
+// "Move on to the next level" (safelife_env.py:204; sl_env_batch.pool_next), by thread 0.  check_env admits no
+// negative level_stride and level_idx is in [0, L), so pos_mod is the plain remainder here; it is written as pos_mod
+// so that the rule does not rest on that check.
+__device__ __forceinline__ void advance_level(const sl_env_batch &env, sl_env_scalars *sc) {
+    sc->level_idx = env.pool_next ? env.pool_next[sc->level_idx] : pos_mod(sc->level_idx + env.level_stride, env.L);
+    sc->episode_idx += 1;
+}
+
+__device__ __forceinline__ void pool_board_to_block(const sl_env_batch &env, int l, u16 *brd) {
+    const int HW = env.H * env.W;
+    const u16 *pb = env.pool_board + (size_t)l * HW;
+    for (int i = threadIdx.x; i < HW; i += GB) brd[i] = pb[i];
+}
+
+// Pool level l into env e: the board into LDS `brd`; goals, exit locations and the episode's generator into the
+// env's global state.  The caller adds the agent locations and places the barrier.
+__device__ __forceinline__ void level_to_block(const sl_env_batch &env, int e, int l, u16 *brd) {
+    const int HW = env.H * env.W, tid = threadIdx.x, E = env.E;
+    const u16 *pb = env.pool_board + (size_t)l * HW, *pg = env.pool_goals + (size_t)l * HW;
+    u16 *gdst = env.goals + (size_t)e * HW;
+    for (int i = tid; i < HW; i += GB) {    // (not pool_board_to_block and a loop for the goals: the two loads of a pass
+        brd[i] = pb[i];                     //  go out together, and a reload is on the step's critical chain)
+        gdst[i] = pg[i];
+    }
+    for (int k = tid; k < E; k += GB) env.exit_locs[(size_t)e * E + k] = env.pool_exit_locs[(size_t)l * E + k];
+    if (tid == 0) {
+        sl_pcg64 gen = env.pool_rng[l];
+        if (env.stream_salt) sl_episode_stream(gen.state_hi, gen.state_lo, env.stream_salt + e, env.scalars[e].episode_idx);
+        env.rng[e] = gen;
+    }
+}
+
+// The second half of game.advance_board (safelife_env.py:152), after the caller's ca_step_block on the board: the goals
+// take a CA step of their own (through `cur`, whose board has moved on, into l.buf[3] and back to `ggoals`) unless they
+// are known to be static.  Returns the goals to score the new board against.
+// (The board's own ca_step_block call stays in the kernels: from inside this function the compiler reads the workgroup
+//  size behind its first barrier with two dependent vector loads instead of one scalar load.)
+__device__ __forceinline__ const u16 *advance_goals(const GenericLds &l, u16 *cur, int H, int W, float inv_w, double p,
+                                                    sl_env_scalars *sc, u16 *ggoals, const Jump *__restrict__ jump) {
+    const int HW = H * W, tid = threadIdx.x;
+    u16 *rows = l.buf[1], *aux = l.buf[3];
+    const int gstatic = sc->goals_static;
+    if (gstatic == 1) return ggoals;
+    for (int i = tid; i < HW; i += GB) cur[i] = ggoals[i];
+    __syncthreads();
+    ca_step_block(cur, rows, aux, H, W, inv_w, p, l.rng, jump, l.wave_tot);
+    int changed = 0;
+    for (int i = tid; i < HW; i += GB) {
+        u16 g = aux[i];
+        changed |= (g != cur[i]) || (g & SPAWNING);
+        ggoals[i] = g;
+    }
+    changed = __syncthreads_or(changed);
+    if (tid == 0 && gstatic == 0) sc->goals_static = changed ? 2 : 1;
+    return aux;
+}
+
+// The step that ends an episode queues it for the side-effect pass (include/safelife_hip.h), by thread 0: `o` is the
+// step's record (agent 0's in a multi-agent env).  Returns the slot, or -1 without a queue or when it is full.
+__device__ __forceinline__ int queue_finished(const sl_env_batch &env, const sl_env_scalars *sc, int e,
+                                              const sl_step_out &o, int steps) {
+    if (env.finished.capacity <= 0) return -1;
+    const int slot = atomicAdd(env.finished.count, 1);
+    if (slot >= env.finished.capacity) return -1;
+    sl_episode_record rec;
+    rec.env = e + env.finished.env_base;
+    rec.level = sc->level_idx;
+    rec.num_steps = steps;
+    rec.episode_idx = sc->episode_idx;
+    rec.spawn_prob = sc->spawn_prob;
+    rec.episode_reward = o.episode_reward;
+    rec.episode_length = o.episode_length;
+    rec.success = o.success;
+    rec.times_up = o.times_up;
+    rec.n_cell_types = rec.reserved = 0;
+    env.finished.records[slot] = rec;
+    return slot;
+}
+// ... and its board, as the agents left it, before any reload
+__device__ __forceinline__ void copy_finished_board(const sl_env_batch &env, int slot, const u16 *nxt) {
+    if (slot < 0) return;
+    const int HW = env.H * env.W;
+    u16 *dst = env.finished.boards + (size_t)slot * HW;
+    for (int i = threadIdx.x; i < HW; i += GB) dst[i] = nxt[i];
+}
+
+// SimpleSideEffectPenalty's count for one env (env_wrappers.py:183-197), in two calls so that the kernel names its
+// baseline between them, behind the barriers.  Exit cells never count (:191-193): flag them in the free `rows` buffer.
+__device__ __forceinline__ void flag_exit_cells(const int32_t *exits, int E, u16 *rows, int HW) {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < HW; i += GB) rows[i] = 0;
+    __syncthreads();
+    for (int k = tid; k < E; k += GB)
+        if (exits[k] >= 0) rows[exits[k]] = 1;
+    __syncthreads();
+}
+// ... then the cells of the new board `nxt` that differ from the baseline, one count per env.  baseline(i) gives cell i
+// of the baseline with the player bits cleared.
+template <class Baseline>
+__device__ __forceinline__ int side_effect_count(const sl_env_batch &env, const u16 *nxt, const u16 *goals,
+                                                 const u16 *rows, int *wave_tot, Baseline baseline) {
+    const int HW = env.H * env.W, tid = threadIdx.x;
+    const bool ignore = (env.wrap.flags & SL_WRAP_IGNORE_REWARD_CELLS) != 0;
+    int mine = 0;
+    for (int i = tid; i < HW; i += GB)
+        if (!rows[i]) mine += side_effect_cell(nxt[i] & 0xFFFFu & ~PLAYER, baseline(i), goals[i], ignore);
+    return block_sum(mine, wave_tot);
+}
+
 // SafeLifeEnv.reset() body for env e: pool level -> LDS board (`brd`) and global per-env state.
 // ivar[0..1] receives the agent location.  All threads participate.
 __device__ void reset_block(const sl_env_batch &env, int e, u16 *brd, int *ivar, int *wave_tot) {
@@ -404,23 +539,14 @@ __device__ void reset_block(const sl_env_batch &env, int e, u16 *brd, int *ivar,
     sl_env_scalars *sc = env.scalars + e;
     const int l = sc->level_idx;
     const sl_level_scalars lv = env.pool_scalars[l];
-    const u16 *pb = env.pool_board + (size_t)l * HW, *pg = env.pool_goals + (size_t)l * HW;
-    u16 *gdst = env.goals + (size_t)e * HW;
-    for (int i = tid; i < HW; i += GB) {
-        brd[i] = pb[i];
-        gdst[i] = pg[i];
-    }
-    for (int k = tid; k < E; k += GB) env.exit_locs[(size_t)e * E + k] = env.pool_exit_locs[(size_t)l * E + k];
+    level_to_block(env, e, l, brd);
     if (tid == 0) {
         ivar[0] = lv.agent_row;
         ivar[1] = lv.agent_col;
-        sl_pcg64 gen = env.pool_rng[l];
-        if (env.stream_salt) sl_episode_stream(gen.state_hi, gen.state_lo, env.stream_salt + e, sc->episode_idx);
-        env.rng[e] = gen;
     }
     __syncthreads();
     const int32_t *table = env.points_table + 72 * lv.table_idx;
-    int score = board_score(brd, pg, HW, table, wave_tot);
+    int score = board_score(brd, env.pool_goals + (size_t)l * HW, HW, table, wave_tot);
     if (tid == 0) {
         const bool open = recolor_exits(brd, env.W, ivar[0], ivar[1], env.pool_exit_locs + (size_t)l * E, E,
                                         score, lv.initial_points, lv.required_reset, env.exit_points);
@@ -448,7 +574,8 @@ __device__ void reset_block(const sl_env_batch &env, int e, u16 *brd, int *ivar,
     __syncthreads();
 }
 
-// ------------------------------------------------------------------------- env step / reset
+// ------------------------------------------------------------------------- env step / reset, single agent
+// The state of the one agent lives in sl_env_scalars; a board may have no agent (ly < 0); T steps per launch.
 
 __global__ __launch_bounds__(GB_MAX) void k_env_rollout_generic(sl_env_batch env,
                                                             const int32_t *__restrict__ actions, int T,
@@ -459,14 +586,16 @@ __global__ __launch_bounds__(GB_MAX) void k_env_rollout_generic(sl_env_batch env
     const int H = env.H, W = env.W, HW = H * W, E = env.E;
     const int e = blockIdx.x, tid = threadIdx.x;
     GenericLds l = carve(smem, HW, 4);
-    u16 *cur = l.buf[0], *rows = l.buf[1], *nxt = l.buf[2], *aux = l.buf[3];
-    int *ivar = l.ivar;   // [0],[1] agent loc; [2] done flag
+    u16 *cur = l.buf[0], *nxt = l.buf[2];
+    int *ivar = l.ivar;   // [0],[1] agent loc; [2] done flag; [3]-[5] reward, times_up, episode reward; [6] queue slot
     u16 *gboard = env.board + (size_t)e * HW;
     u16 *ggoals = env.goals + (size_t)e * HW;
     sl_env_scalars *sc = env.scalars + e;
     const int32_t *exits = env.exit_locs + (size_t)e * E;
     const float inv_w = 1.0f / (float)W;
 
+    // (block_load / block_store written out, here and in the reload below: through the calls this kernel measures slower,
+    //  profiles/generic_step_phases_ab.json)
     for (int i = tid; i < HW; i += GB) cur[i] = gboard[i];
     if (tid < 4) l.rng[tid] = ((const u64 *)(env.rng + e))[tid];
     if (tid == 0) {
@@ -481,23 +610,8 @@ __global__ __launch_bounds__(GB_MAX) void k_env_rollout_generic(sl_env_batch env
         __syncthreads();
         // safelife_env.py:152  game.advance_board (board, then goals unless static)
         const double p = (double)sc->spawn_prob;
-        ca_step_block(cur, rows, nxt, H, W, inv_w, p, l.rng, jump, l.wave_tot);
-        const u16 *goals = ggoals;
-        const int gstatic = sc->goals_static;
-        if (gstatic != 1) {
-            for (int i = tid; i < HW; i += GB) cur[i] = ggoals[i];
-            __syncthreads();
-            ca_step_block(cur, rows, aux, H, W, inv_w, p, l.rng, jump, l.wave_tot);
-            int changed = 0;
-            for (int i = tid; i < HW; i += GB) {
-                u16 g = aux[i];
-                changed |= (g != cur[i]) || (g & SPAWNING);
-                ggoals[i] = g;
-            }
-            changed = __syncthreads_or(changed);
-            if (tid == 0 && gstatic == 0) sc->goals_static = changed ? 2 : 1;
-            goals = aux;
-        }
+        ca_step_block(cur, l.buf[1], nxt, H, W, inv_w, p, l.rng, jump, l.wave_tot);
+        const u16 *goals = advance_goals(l, cur, H, W, inv_w, p, sc, ggoals, jump);
         // safelife_env.py:153-160
         const int32_t *table = env.points_table + 72 * sc->table_idx;
         int score = board_score(nxt, goals, HW, table, l.wave_tot);
@@ -543,55 +657,22 @@ __global__ __launch_bounds__(GB_MAX) void k_env_rollout_generic(sl_env_batch env
             ivar[3] = __float_as_int(reward);
             ivar[4] = times_up;
             ivar[5] = __float_as_int(ep_r);
-            // the step that ends the episode queues it for the side-effect pass (include/safelife_hip.h)
-            int slot = -1;
-            if (env.finished.capacity > 0 && done && active) {
-                slot = atomicAdd(env.finished.count, 1);
-                if (slot < env.finished.capacity) {
-                    sl_episode_record rec;
-                    rec.env = e + env.finished.env_base;
-                    rec.level = sc->level_idx;
-                    rec.num_steps = steps;
-                    rec.episode_idx = sc->episode_idx;
-                    rec.spawn_prob = sc->spawn_prob;
-                    rec.episode_reward = ep_r;
-                    rec.episode_length = ep_l;
-                    rec.success = success;
-                    rec.times_up = times_up;
-                    rec.n_cell_types = rec.reserved = 0;
-                    env.finished.records[slot] = rec;
-                } else {
-                    slot = -1;
-                }
-            }
-            ivar[6] = slot;
+            ivar[6] = (done && active) ? queue_finished(env, sc, e, o, steps) : -1;
         }
         __syncthreads();
-        if (ivar[6] >= 0) {
-            u16 *dst = env.finished.boards + (size_t)ivar[6] * HW;
-            for (int i = tid; i < HW; i += GB) dst[i] = nxt[i];
-        }
+        copy_finished_board(env, ivar[6], nxt);
         if (env.wrap.flags) {       // env_wrappers.py: movement bonus, exit bonus, side-effect penalty
             int side = 0;
             if (env.wrap.flags & SL_WRAP_SIDE_EFFECT) {
-                // exit cells never count (env_wrappers.py:191-193): flag them in the free `rows` buffer
-                for (int i = tid; i < HW; i += GB) rows[i] = 0;
-                __syncthreads();
-                for (int k = tid; k < E; k += GB)
-                    if (exits[k] >= 0) rows[exits[k]] = 1;
-                __syncthreads();
+                // "starting-state": the pool level with its exits as the reset left them; "inaction": the baseline board
+                // k_inaction_generic advanced just before this launch
+                flag_exit_cells(exits, E, l.buf[1], HW);
                 const u16 *pb = env.pool_board + (size_t)sc->level_idx * HW;
-                // "inaction": the baseline board k_inaction_generic advanced just before this launch
                 const u16 *ib = (env.wrap.flags & SL_WRAP_INACTION) ? env.wrap.inaction_board + (size_t)e * HW : nullptr;
                 const bool open = sc->exit_open_at_reset != 0;
-                const bool ignore = (env.wrap.flags & SL_WRAP_IGNORE_REWARD_CELLS) != 0;
-                int mine = 0;
-                for (int i = tid; i < HW; i += GB)
-                    if (!rows[i])
-                        mine += side_effect_cell(nxt[i] & 0xFFFFu & ~PLAYER,
-                                                 ib ? (u32)ib[i] & ~PLAYER : baseline_cell(pb[i], false, open),
-                                                 goals[i], ignore);
-                side = block_sum(mine, l.wave_tot);
+                side = side_effect_count(env, nxt, goals, l.buf[1], l.wave_tot, [=](int i) {
+                    return ib ? (u32)ib[i] & ~PLAYER : baseline_cell(pb[i], false, open);
+                });
             }
             if (tid == 0) {
                 const double shaped = wrap_step(env.wrap, env.wrap.state[e], env.wrap.move_table,
@@ -602,14 +683,11 @@ __global__ __launch_bounds__(GB_MAX) void k_env_rollout_generic(sl_env_batch env
             }
             __syncthreads();
         }
-        u16 *sw = cur;
+        u16 *sw = cur;      // the new board is the next step's current one
         cur = nxt;
         nxt = sw;
         if (env.auto_reset && ivar[2]) {
-            if (tid == 0) {
-                sc->level_idx = env.pool_next ? env.pool_next[sc->level_idx] : (sc->level_idx + env.level_stride) % env.L;
-                sc->episode_idx += 1;
-            }
+            if (tid == 0) advance_level(env, sc);
             __syncthreads();
             reset_block(env, e, cur, ivar, l.wave_tot);
             if (tid < 4) l.rng[tid] = ((const u64 *)(env.rng + e))[tid];
@@ -627,15 +705,33 @@ __global__ __launch_bounds__(GB_MAX) void k_env_rollout_generic(sl_env_batch env
     write_obs(env, e, cur, ggoals, ivar[0], ivar[1], exits);
 }
 
+__global__ __launch_bounds__(GB_MAX) void k_env_reset_generic(sl_env_batch env,
+                                                          const uint8_t *__restrict__ mask) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int HW = env.H * env.W, e = blockIdx.x, tid = threadIdx.x;
+    if (mask && !mask[e]) return;
+    GenericLds l = carve(smem, HW, 1);
+    // a slot that already holds a level moves on to its next one (safelife_env.py:204)
+    if (tid == 0 && env.scalars[e].loaded) advance_level(env, env.scalars + e);
+    __syncthreads();
+    reset_block(env, e, l.buf[0], l.ivar, l.wave_tot);
+    u16 *gboard = env.board + (size_t)e * HW;
+    for (int i = tid; i < HW; i += GB) gboard[i] = l.buf[0][i];
+    write_obs(env, e, l.buf[0], env.goals + (size_t)e * HW, l.ivar[0], l.ivar[1],
+              env.exit_locs + (size_t)e * env.E);
+}
+
 // ------------------------------------------------------------------------- multi-agent env step / reset
 // SafeLifeEnv(single_agent=False): include/safelife_hip.h, sl_multi_agent.  One workgroup per board; what concerns a
-// single agent is serial work of thread 0, in agent order (advance_board.c:217-220; safelife_game.py:537-552).
+// single agent is serial work of thread 0, in agent order (advance_board.c:217-220; safelife_game.py:537-552).  The
+// kernels are the single-agent ones' phases (above) around per-agent state: sl_agent_state in place of sl_env_scalars'
+// agent fields, every agent on the board (no ly < 0), one step per launch, wrap_step_multi in place of wrap_step.
 
 // per-agent words shared by the workgroup, behind the four board buffers of the dynamic LDS
 struct MultiLds {
     int *loc;       // [2 A]
     int *score;     // [A]  sum(points_table[a] * alive_counts)
-    int *flag;      // [0] every agent is done
+    int *flag;      // [0] every agent is done; [1] some agent was active; [2] queue slot
     uint8_t *stage; // one observation's channel bytes (write_obs), or null
 };
 __device__ __forceinline__ MultiLds carve_multi(unsigned char *smem, int HW, bool staged) {
@@ -650,17 +746,42 @@ static size_t multi_lds_bytes(const sl_env_batch &env, const sl_multi_agent &m) 
     return generic_lds_bytes(env.H * env.W, 4) + 4 * SL_MAX_AGENTS * sizeof(int) + multi_stage_bytes(env, m);
 }
 
+// The agents' locations (sl_agent_state or sl_level_agent) into ml.loc.  The caller places the barrier.
+template <class Agent>
+__device__ __forceinline__ void agent_locs(const Agent *agents, int A, MultiLds ml) {
+    const int tid = threadIdx.x;
+    if (tid < A) {
+        ml.loc[2 * tid] = agents[tid].row;
+        ml.loc[2 * tid + 1] = agents[tid].col;
+    }
+}
+
+// Every agent's score into ml.score: its own table (sl_agent_state or sl_level_agent .table_idx) against the shared
+// counts (safelife_game.py:684-687).  Ends with the scores visible to the whole workgroup.
+template <class Agent>
+__device__ __forceinline__ void score_agents(const u16 *board, const u16 *goals, int HW, const sl_env_batch &env,
+                                             const Agent *agents, int A, MultiLds ml, int *wave_tot) {
+    for (int a = 0; a < A; ++a) {
+        const int s = board_score(board, goals, HW, env.points_table + 72 * agents[a].table_idx, wave_tot);
+        if (threadIdx.x == 0) ml.score[a] = s;
+    }
+    __syncthreads();
+}
+
 // GameState.update_exit_colors for A agents (safelife_game.py:537-552), by thread 0: every agent's cell gets the EXIT bit
 // iff THAT agent may leave (its own points against its own requirement); the exits turn red when any agent may.
-__device__ bool recolor_exits_multi(u16 *board, int W, const int *loc, const int *score, int A, const sl_agent_state *ag,
-                                    const int *required, const int32_t *exits, int E, int exit_points) {
+// points(a) gives agent a's (initial points, required points): the level's at a reset, the agent's own during a step.
+template <class Points>
+__device__ bool recolor_exits_multi(u16 *board, int W, const int *loc, const int *score, int A, Points points,
+                                    const int32_t *exits, int E, int exit_points) {
     bool can[SL_MAX_AGENTS];
     bool any_can = false;
     for (int a = 0; a < A; ++a) {           // can_exit() is evaluated on the board as it stands, for all agents, first
         const u32 cell = board[loc[2 * a] * W + loc[2 * a + 1]];
-        int earned = score[a] - ag[a].initial_points + exit_points * (has_exited(cell) ? 1 : 0);
+        const int2 p = points(a);
+        int earned = score[a] - p.x + exit_points * (has_exited(cell) ? 1 : 0);
         if (earned < 0) earned = 0;
-        can[a] = (cell & AGENT) && earned >= required[a];
+        can[a] = (cell & AGENT) && earned >= p.y;
         any_can = any_can || can[a];
     }
     for (int a = 0; a < A; ++a) {
@@ -673,6 +794,14 @@ __device__ bool recolor_exits_multi(u16 *board, int W, const int *loc, const int
         if (ex >= 0) board[ex] = paint;
     }
     return any_can;
+}
+
+// Recolor the fresh pool level l in `brd` for its A agents (ml.loc, ml.score), by thread 0.
+__device__ __forceinline__ void level_exits_multi(const sl_env_batch &env, const sl_level_agent *pa, int A, int l,
+                                                  u16 *brd, MultiLds ml) {
+    recolor_exits_multi(brd, env.W, ml.loc, ml.score, A,
+                        [=](int a) { return make_int2(pa[a].initial_points, pa[a].required_reset); },
+                        env.pool_exit_locs + (size_t)l * env.E, env.E, env.exit_points);
 }
 
 // The wrappers' reset() for the agents of env e (sl_multi_extras), after reset_block_multi: each agent's trail starts
@@ -689,41 +818,18 @@ __device__ __forceinline__ void wrap_reset_multi(const sl_env_batch &env, const 
 
 // SafeLifeEnv.reset() body of a multi-agent env: pool level -> LDS board and the per-env / per-agent state.
 __device__ void reset_block_multi(const sl_env_batch &env, const sl_multi_agent &m, int e, u16 *brd, MultiLds ml, int *wave_tot) {
-    const int HW = env.H * env.W, tid = threadIdx.x, E = env.E, A = m.n_agents;
+    const int HW = env.H * env.W, tid = threadIdx.x, A = m.n_agents;
     sl_env_scalars *sc = env.scalars + e;
     const int l = sc->level_idx;
     const sl_level_scalars lv = env.pool_scalars[l];
     const sl_level_agent *pa = m.pool_agents + (size_t)l * A;
     sl_agent_state *ag = m.agents + (size_t)e * A;
-    const u16 *pb = env.pool_board + (size_t)l * HW, *pg = env.pool_goals + (size_t)l * HW;
-    u16 *gdst = env.goals + (size_t)e * HW;
-    for (int i = tid; i < HW; i += GB) {
-        brd[i] = pb[i];
-        gdst[i] = pg[i];
-    }
-    for (int k = tid; k < E; k += GB) env.exit_locs[(size_t)e * E + k] = env.pool_exit_locs[(size_t)l * E + k];
-    if (tid < A) {
-        ml.loc[2 * tid] = pa[tid].row;
-        ml.loc[2 * tid + 1] = pa[tid].col;
-    }
-    if (tid == 0) {
-        sl_pcg64 gen = env.pool_rng[l];
-        if (env.stream_salt) sl_episode_stream(gen.state_hi, gen.state_lo, env.stream_salt + e, sc->episode_idx);
-        env.rng[e] = gen;
-    }
+    level_to_block(env, e, l, brd);
+    agent_locs(pa, A, ml);
     __syncthreads();
-    for (int a = 0; a < A; ++a) {
-        const int s = board_score(brd, pg, HW, env.points_table + 72 * pa[a].table_idx, wave_tot);
-        if (tid == 0) ml.score[a] = s;
-    }
-    __syncthreads();
+    score_agents(brd, env.pool_goals + (size_t)l * HW, HW, env, pa, A, ml, wave_tot);
     if (tid == 0) {
-        int required[SL_MAX_AGENTS];
-        for (int a = 0; a < A; ++a) {
-            ag[a].initial_points = pa[a].initial_points;
-            required[a] = pa[a].required_reset;
-        }
-        recolor_exits_multi(brd, env.W, ml.loc, ml.score, A, ag, required, env.pool_exit_locs + (size_t)l * E, E, env.exit_points);
+        level_exits_multi(env, pa, A, l, brd, ml);
         for (int a = 0; a < A; ++a) {
             const int exited = has_exited(brd[ml.loc[2 * a] * env.W + ml.loc[2 * a + 1]]) ? 1 : 0;
             sl_agent_state n;
@@ -769,54 +875,31 @@ __global__ __launch_bounds__(GB_MAX) void k_env_step_multi(sl_env_batch env, sl_
     const int e = blockIdx.x, tid = threadIdx.x;
     GenericLds l = carve(smem, HW, 4);
     MultiLds ml = carve_multi(smem, HW, m.obs && env.n_channels > 0);
-    u16 *cur = l.buf[0], *rows = l.buf[1], *nxt = l.buf[2], *aux = l.buf[3];
+    u16 *const cur = l.buf[0], *const nxt = l.buf[2];   // the board before the step; after it, and the fresh level
     u16 *gboard = env.board + (size_t)e * HW;
     u16 *ggoals = env.goals + (size_t)e * HW;
     sl_env_scalars *sc = env.scalars + e;
     sl_agent_state *ag = m.agents + (size_t)e * A;
     const int32_t *exits = env.exit_locs + (size_t)e * E;
-    const float inv_w = 1.0f / (float)W;
 
-    for (int i = tid; i < HW; i += GB) cur[i] = gboard[i];
-    if (tid < 4) l.rng[tid] = ((const u64 *)(env.rng + e))[tid];
-    if (tid < A) {
-        ml.loc[2 * tid] = ag[tid].row;
-        ml.loc[2 * tid + 1] = ag[tid].col;
-    }
+    block_load(l, cur, gboard, HW, env.rng + e);
+    agent_locs(ag, A, ml);
     __syncthreads();
     // safelife_env.py:151  game.execute_actions: every agent's action, in index order (advance_board.c:217-220)
     if (tid == 0)
         for (int a = 0; a < A; ++a) act_one<int>(cur, H, W, ml.loc + 2 * a, actions[(size_t)e * A + a]);
     __syncthreads();
     // safelife_env.py:152  game.advance_board (board, then goals unless static)
+    const float inv_w = 1.0f / (float)W;
     const double p = (double)sc->spawn_prob;
-    ca_step_block(cur, rows, nxt, H, W, inv_w, p, l.rng, jump, l.wave_tot);
-    const u16 *goals = ggoals;
-    const int gstatic = sc->goals_static;
-    if (gstatic != 1) {
-        for (int i = tid; i < HW; i += GB) cur[i] = ggoals[i];
-        __syncthreads();
-        ca_step_block(cur, rows, aux, H, W, inv_w, p, l.rng, jump, l.wave_tot);
-        int changed = 0;
-        for (int i = tid; i < HW; i += GB) {
-            u16 g = aux[i];
-            changed |= (g != cur[i]) || (g & SPAWNING);
-            ggoals[i] = g;
-        }
-        changed = __syncthreads_or(changed);
-        if (tid == 0 && gstatic == 0) sc->goals_static = changed ? 2 : 1;
-        goals = aux;
-    }
-    // safelife_env.py:153-160, per agent: its own table against the shared counts (safelife_game.py:684-687)
-    for (int a = 0; a < A; ++a) {
-        const int s = board_score(nxt, goals, HW, env.points_table + 72 * ag[a].table_idx, l.wave_tot);
-        if (tid == 0) ml.score[a] = s;
-    }
-    __syncthreads();
+    ca_step_block(cur, l.buf[1], nxt, H, W, inv_w, p, l.rng, jump, l.wave_tot);
+    const u16 *goals = advance_goals(l, cur, H, W, inv_w, p, sc, ggoals, jump);
+    // safelife_env.py:153-160, per agent
+    score_agents(nxt, goals, HW, env, ag, A, ml, l.wave_tot);
     if (tid == 0) {
-        int required[SL_MAX_AGENTS];
-        for (int a = 0; a < A; ++a) required[a] = ag[a].required_points;
-        recolor_exits_multi(nxt, W, ml.loc, ml.score, A, ag, required, exits, E, env.exit_points);
+        recolor_exits_multi(nxt, W, ml.loc, ml.score, A,
+                            [=](int a) { return make_int2(ag[a].initial_points, ag[a].required_points); }, exits, E,
+                            env.exit_points);
         const int steps = sc->num_steps + 1;
         sc->num_steps = steps;
         const bool times_up = steps >= env.time_limit;
@@ -853,56 +936,24 @@ __global__ __launch_bounds__(GB_MAX) void k_env_step_multi(sl_env_batch env, sl_
     }
     __syncthreads();
     if (EX) {
-        // the step on which every agent is done ends the env's episode: queue it for the side-effect pass
-        // (safelife_env.py:183-192 scores it once, when np.all(done) first holds), with every agent's record
+        // the step on which every agent is done ends the env's episode (safelife_env.py:183-192 scores it once, when
+        // np.all(done) first holds): agent 0's record in the queue, every agent's next to it
         if (tid == 0) {
-            int slot = -1;
-            if (env.finished.capacity > 0 && ml.flag[0] && ml.flag[1]) {
-                slot = atomicAdd(env.finished.count, 1);
-                if (slot < env.finished.capacity) {
-                    const sl_step_out o0 = m.out[(size_t)e * A];
-                    sl_episode_record rec;
-                    rec.env = e + env.finished.env_base;
-                    rec.level = sc->level_idx;
-                    rec.num_steps = sc->num_steps;
-                    rec.episode_idx = sc->episode_idx;
-                    rec.spawn_prob = sc->spawn_prob;
-                    rec.episode_reward = o0.episode_reward;
-                    rec.episode_length = o0.episode_length;
-                    rec.success = o0.success;
-                    rec.times_up = o0.times_up;
-                    rec.n_cell_types = rec.reserved = 0;
-                    env.finished.records[slot] = rec;
-                    for (int a = 0; a < A; ++a) x.finished_agents[(size_t)slot * A + a] = m.out[(size_t)e * A + a];
-                } else {
-                    slot = -1;
-                }
-            }
+            const int slot = (ml.flag[0] && ml.flag[1]) ? queue_finished(env, sc, e, m.out[(size_t)e * A], sc->num_steps) : -1;
+            for (int a = 0; slot >= 0 && a < A; ++a) x.finished_agents[(size_t)slot * A + a] = m.out[(size_t)e * A + a];
             ml.flag[2] = slot;
         }
         __syncthreads();
-        if (ml.flag[2] >= 0) {      // the board as the agents left it, before any reload
-            u16 *dst = env.finished.boards + (size_t)ml.flag[2] * HW;
-            for (int i = tid; i < HW; i += GB) dst[i] = nxt[i];
-        }
+        copy_finished_board(env, ml.flag[2], nxt);
         if (env.wrap.flags) {       // env_wrappers.py over every agent: movement bonus, exit bonus, side-effect penalty
             int side = 0;
             if (env.wrap.flags & SL_WRAP_SIDE_EFFECT) {
-                // one count per env; exit cells never count (env_wrappers.py:191-193): flag them in the free `rows` buffer
-                for (int i = tid; i < HW; i += GB) rows[i] = 0;
-                __syncthreads();
-                for (int k = tid; k < E; k += GB)
-                    if (exits[k] >= 0) rows[exits[k]] = 1;
-                __syncthreads();
                 // "starting-state": the level as the multi-agent reset left it; "inaction": the board k_inaction_generic
                 // advanced just before this launch
+                flag_exit_cells(exits, E, l.buf[1], HW);
                 const u16 *b0 = (env.wrap.flags & SL_WRAP_INACTION) ? env.wrap.inaction_board + (size_t)e * HW
                                                                      : x.baseline + (size_t)sc->level_idx * HW;
-                const bool ignore = (env.wrap.flags & SL_WRAP_IGNORE_REWARD_CELLS) != 0;
-                int mine = 0;
-                for (int i = tid; i < HW; i += GB)
-                    if (!rows[i]) mine += side_effect_cell(nxt[i] & 0xFFFFu & ~PLAYER, (u32)b0[i] & ~PLAYER, goals[i], ignore);
-                side = block_sum(mine, l.wave_tot);
+                side = side_effect_count(env, nxt, goals, l.buf[1], l.wave_tot, [=](int i) { return (u32)b0[i] & ~PLAYER; });
             }
             if (tid == 0)
                 for (int a = 0; a < A; ++a) {
@@ -915,26 +966,19 @@ __global__ __launch_bounds__(GB_MAX) void k_env_step_multi(sl_env_batch env, sl_
             __syncthreads();
         }
     }
-    u16 *sw = cur;
-    cur = nxt;
-    nxt = sw;
     if (env.auto_reset && ml.flag[0]) {     // training/base_algo.py:231-236: a fresh level once every agent is done
-        if (tid == 0) {
-            sc->level_idx = env.pool_next ? env.pool_next[sc->level_idx] : (sc->level_idx + env.level_stride) % env.L;
-            sc->episode_idx += 1;
-        }
+        if (tid == 0) advance_level(env, sc);
         __syncthreads();
-        reset_block_multi(env, m, e, cur, ml, l.wave_tot);
-        if (EX) wrap_reset_multi(env, x, e, A, cur, ml.loc);
-        if (tid < 4) l.rng[tid] = ((const u64 *)(env.rng + e))[tid];
+        reset_block_multi(env, m, e, nxt, ml, l.wave_tot);
+        if (EX) wrap_reset_multi(env, x, e, A, nxt, ml.loc);
+        rng_load(l, env.rng + e);
         __syncthreads();
     }
-    for (int i = tid; i < HW; i += GB) gboard[i] = cur[i];
-    if (tid < 4) ((u64 *)(env.rng + e))[tid] = l.rng[tid];
+    block_store(l, nxt, gboard, HW, env.rng + e);
     __syncthreads();   // goals written by this workgroup are read back below
     if (m.obs || (EX && env.policy_obs))
         for (int a = 0; a < A; ++a)
-            write_obs(env, e, cur, ggoals, ml.loc[2 * a], ml.loc[2 * a + 1], exits, m.obs, e * A + a, ml.stage);
+            write_obs(env, e, nxt, ggoals, ml.loc[2 * a], ml.loc[2 * a + 1], exits, m.obs, e * A + a, ml.stage);
 }
 
 template <bool EX>
@@ -945,13 +989,8 @@ __global__ __launch_bounds__(GB_MAX) void k_env_reset_multi(sl_env_batch env, sl
     if (mask && !mask[e]) return;
     GenericLds l = carve(smem, HW, 4);
     MultiLds ml = carve_multi(smem, HW, m.obs && env.n_channels > 0);
-    if (tid == 0) {         // a slot that already holds a level moves on to its next one (safelife_env.py:204)
-        sl_env_scalars *sc = env.scalars + e;
-        if (sc->loaded) {
-            sc->level_idx = env.pool_next ? env.pool_next[sc->level_idx] : pos_mod(sc->level_idx + env.level_stride, env.L);
-            sc->episode_idx += 1;
-        }
-    }
+    // a slot that already holds a level moves on to its next one (safelife_env.py:204)
+    if (tid == 0 && env.scalars[e].loaded) advance_level(env, env.scalars + e);
     __syncthreads();
     reset_block_multi(env, m, e, l.buf[0], ml, l.wave_tot);
     if (EX) wrap_reset_multi(env, x, e, A, l.buf[0], ml.loc);
@@ -974,52 +1013,14 @@ __global__ __launch_bounds__(GB_MAX) void k_multi_baseline(sl_env_batch env, sl_
     MultiLds ml = carve_multi(smem, HW, false);
     u16 *brd = g.buf[0];
     const sl_level_agent *pa = m.pool_agents + (size_t)l * A;
-    const u16 *pb = env.pool_board + (size_t)l * HW, *pg = env.pool_goals + (size_t)l * HW;
-    for (int i = tid; i < HW; i += GB) brd[i] = pb[i];
-    if (tid < A) {
-        ml.loc[2 * tid] = pa[tid].row;
-        ml.loc[2 * tid + 1] = pa[tid].col;
-    }
+    pool_board_to_block(env, l, brd);
+    agent_locs(pa, A, ml);
     __syncthreads();
-    for (int a = 0; a < A; ++a) {
-        const int s = board_score(brd, pg, HW, env.points_table + 72 * pa[a].table_idx, g.wave_tot);
-        if (tid == 0) ml.score[a] = s;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        sl_agent_state ag[SL_MAX_AGENTS];
-        int required[SL_MAX_AGENTS];
-        for (int a = 0; a < A; ++a) {
-            ag[a].initial_points = pa[a].initial_points;
-            required[a] = pa[a].required_reset;
-        }
-        recolor_exits_multi(brd, env.W, ml.loc, ml.score, A, ag, required, env.pool_exit_locs + (size_t)l * env.E, env.E,
-                            env.exit_points);
-    }
+    score_agents(brd, env.pool_goals + (size_t)l * HW, HW, env, pa, A, ml, g.wave_tot);
+    if (tid == 0) level_exits_multi(env, pa, A, l, brd, ml);
     __syncthreads();
     u16 *dst = baseline + (size_t)l * HW;
     for (int i = tid; i < HW; i += GB) dst[i] = brd[i];
-}
-
-__global__ __launch_bounds__(GB_MAX) void k_env_reset_generic(sl_env_batch env,
-                                                          const uint8_t *__restrict__ mask) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int HW = env.H * env.W, e = blockIdx.x, tid = threadIdx.x;
-    if (mask && !mask[e]) return;
-    GenericLds l = carve(smem, HW, 1);
-    if (tid == 0) {         // a slot that already holds a level moves on to its next one (safelife_env.py:204)
-        sl_env_scalars *sc = env.scalars + e;
-        if (sc->loaded) {
-            sc->level_idx = env.pool_next ? env.pool_next[sc->level_idx] : pos_mod(sc->level_idx + env.level_stride, env.L);
-            sc->episode_idx += 1;
-        }
-    }
-    __syncthreads();
-    reset_block(env, e, l.buf[0], l.ivar, l.wave_tot);
-    u16 *gboard = env.board + (size_t)e * HW;
-    for (int i = tid; i < HW; i += GB) gboard[i] = l.buf[0][i];
-    write_obs(env, e, l.buf[0], env.goals + (size_t)e * HW, l.ivar[0], l.ivar[1],
-              env.exit_locs + (size_t)e * env.E);
 }
 
 __global__ __launch_bounds__(GB_MAX) void k_env_obs_generic(sl_env_batch env) {
@@ -1062,20 +1063,20 @@ hipError_t launch_obs_to_policy(const u32 *view, int B, int vh, int vw, const sl
     return hipGetLastError();
 }
 
-
-static hipError_t set_lds(const void *fn, size_t bytes) {
-    return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+// The family's launch: n workgroups of generic_threads(HW), one per board (or pool level), with `lds` bytes of dynamic LDS.
+template <class... P, class... Args>
+static hipError_t launch_per_board(void (*kernel)(P...), int n, int HW, size_t lds, hipStream_t stream, Args... args) {
+    hipError_t err = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL(kernel, dim3(n), dim3(generic_threads(HW)), lds, stream, args...);
+    return hipGetLastError();
 }
 
 hipError_t launch_advance_generic(const u16 *in, u16 *out, int B, int H, int W, const float *spawn_prob,
                                   int n_steps, sl_pcg64 *rng, const Jump *jump, int32_t *occupancy,
                                   hipStream_t stream, const int32_t *n_each, const int32_t *n_valid) {
-    size_t lds = generic_lds_bytes(H * W, 3);
-    hipError_t err = set_lds((const void *)k_advance_generic, lds);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(k_advance_generic, dim3(B), dim3(generic_threads(H * W)), lds, stream, in, out, H, W, spawn_prob,
-                       n_steps, rng, jump, occupancy, n_each, n_valid);
-    return hipGetLastError();
+    return launch_per_board(k_advance_generic, B, H * W, generic_lds_bytes(H * W, 3), stream, in, out, H, W, spawn_prob,
+                            n_steps, rng, jump, occupancy, n_each, n_valid);
 }
 
 bool occupancy_generic_supports(int H, int W, int n_steps) {
@@ -1087,12 +1088,8 @@ hipError_t launch_occupancy_generic(const u16 *in, int32_t *counts, size_t count
                                     int n_steps, sl_pcg64 *rng, const Jump *jump, hipStream_t stream) {
     if (!occupancy_generic_supports(H, W, n_steps)) return hipErrorInvalidValue;    // (uint16 counters, 160 KB of LDS)
     if (B <= 0) return hipSuccess;
-    const size_t lds = occupancy_lds_bytes(H * W);
-    hipError_t err = set_lds((const void *)k_occupancy_generic, lds);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(k_occupancy_generic, dim3(B), dim3(generic_threads(H * W)), lds, stream, in, counts, counts_stride, B,
-                       n_valid, valid_period, pre_steps, H, W, spawn_prob, n_steps, rng, jump);
-    return hipGetLastError();
+    return launch_per_board(k_occupancy_generic, B, H * W, occupancy_lds_bytes(H * W), stream, in, counts, counts_stride, B,
+                            n_valid, valid_period, pre_steps, H, W, spawn_prob, n_steps, rng, jump);
 }
 
 hipError_t launch_alive_counts(const u16 *board, const u16 *goals, int B, int HW, int64_t *out,
@@ -1111,76 +1108,41 @@ hipError_t launch_execute_actions(u16 *board, int B, int H, int W, int64_t *locs
 hipError_t launch_env_rollout_generic(const sl_env_batch &env, const int32_t *actions, int T,
                                       float *reward_t, uint8_t *done_t, const Jump *jump,
                                       hipStream_t stream) {
-    size_t lds = generic_lds_bytes(env.H * env.W, 4);
-    hipError_t err = set_lds((const void *)k_env_rollout_generic, lds);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(k_env_rollout_generic, dim3(env.B), dim3(generic_threads(env.H * env.W)), lds, stream, env, actions, T,
-                       reward_t, done_t, jump);
-    return hipGetLastError();
+    const int HW = env.H * env.W;
+    return launch_per_board(k_env_rollout_generic, env.B, HW, generic_lds_bytes(HW, 4), stream, env, actions, T, reward_t,
+                            done_t, jump);
 }
 
 hipError_t launch_inaction_generic(const sl_env_batch &env, const Jump *jump, hipStream_t stream) {
-    size_t lds = generic_lds_bytes(env.H * env.W, 3);
-    hipError_t err = set_lds((const void *)k_inaction_generic, lds);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(k_inaction_generic, dim3(env.B), dim3(generic_threads(env.H * env.W)), lds, stream, env, jump);
-    return hipGetLastError();
+    const int HW = env.H * env.W;
+    return launch_per_board(k_inaction_generic, env.B, HW, generic_lds_bytes(HW, 3), stream, env, jump);
 }
 
 hipError_t launch_env_reset_generic(const sl_env_batch &env, const uint8_t *mask, hipStream_t stream) {
-    size_t lds = generic_lds_bytes(env.H * env.W, 1);
-    hipError_t err = set_lds((const void *)k_env_reset_generic, lds);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(k_env_reset_generic, dim3(env.B), dim3(generic_threads(env.H * env.W)), lds, stream, env, mask);
-    return hipGetLastError();
+    const int HW = env.H * env.W;
+    return launch_per_board(k_env_reset_generic, env.B, HW, generic_lds_bytes(HW, 1), stream, env, mask);
 }
 
+// (x: the training stack's buffers, or null for the plain kernels, which get an empty sl_multi_extras)
 hipError_t launch_env_step_multi(const sl_env_batch &env, const sl_multi_agent &m, const int32_t *actions, const Jump *jump,
                                  hipStream_t stream, const sl_multi_extras *x) {
-    const size_t lds = multi_lds_bytes(env, m);
-    const void *fn = x ? (const void *)k_env_step_multi<true> : (const void *)k_env_step_multi<false>;
-    hipError_t err = set_lds(fn, lds);
-    if (err != hipSuccess) return err;
-    const sl_multi_extras none = {};
-    if (x)
-        hipLaunchKernelGGL(k_env_step_multi<true>, dim3(env.B), dim3(generic_threads(env.H * env.W)), lds, stream, env, m, *x,
-                           actions, jump);
-    else
-        hipLaunchKernelGGL(k_env_step_multi<false>, dim3(env.B), dim3(generic_threads(env.H * env.W)), lds, stream, env, m,
-                           none, actions, jump);
-    return hipGetLastError();
+    return launch_per_board(x ? k_env_step_multi<true> : k_env_step_multi<false>, env.B, env.H * env.W,
+                            multi_lds_bytes(env, m), stream, env, m, x ? *x : sl_multi_extras{}, actions, jump);
 }
 
 hipError_t launch_env_reset_multi(const sl_env_batch &env, const sl_multi_agent &m, const uint8_t *mask, hipStream_t stream,
                                   const sl_multi_extras *x) {
-    const size_t lds = multi_lds_bytes(env, m);
-    const void *fn = x ? (const void *)k_env_reset_multi<true> : (const void *)k_env_reset_multi<false>;
-    hipError_t err = set_lds(fn, lds);
-    if (err != hipSuccess) return err;
-    const sl_multi_extras none = {};
-    if (x)
-        hipLaunchKernelGGL(k_env_reset_multi<true>, dim3(env.B), dim3(generic_threads(env.H * env.W)), lds, stream, env, m, *x,
-                           mask);
-    else
-        hipLaunchKernelGGL(k_env_reset_multi<false>, dim3(env.B), dim3(generic_threads(env.H * env.W)), lds, stream, env, m,
-                           none, mask);
-    return hipGetLastError();
+    return launch_per_board(x ? k_env_reset_multi<true> : k_env_reset_multi<false>, env.B, env.H * env.W,
+                            multi_lds_bytes(env, m), stream, env, m, x ? *x : sl_multi_extras{}, mask);
 }
 
 hipError_t launch_multi_baseline(const sl_env_batch &env, const sl_multi_agent &m, uint16_t *baseline, hipStream_t stream) {
-    const size_t lds = multi_lds_bytes(env, m);
-    hipError_t err = set_lds((const void *)k_multi_baseline, lds);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(k_multi_baseline, dim3(env.L), dim3(generic_threads(env.H * env.W)), lds, stream, env, m, baseline);
-    return hipGetLastError();
+    return launch_per_board(k_multi_baseline, env.L, env.H * env.W, multi_lds_bytes(env, m), stream, env, m, baseline);
 }
 
 hipError_t launch_env_obs_generic(const sl_env_batch &env, hipStream_t stream) {
-    size_t lds = generic_lds_bytes(env.H * env.W, 1);
-    hipError_t err = set_lds((const void *)k_env_obs_generic, lds);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(k_env_obs_generic, dim3(env.B), dim3(generic_threads(env.H * env.W)), lds, stream, env);
-    return hipGetLastError();
+    const int HW = env.H * env.W;
+    return launch_per_board(k_env_obs_generic, env.B, HW, generic_lds_bytes(HW, 1), stream, env);
 }
 
 // ---- do two streams run concurrently? -----------------------------------------------------------------
