@@ -2845,6 +2845,23 @@ __global__ __launch_bounds__(64 * WAVES,
             int r2 = r;
             asm volatile("" : "+v"(r2));
             level = new_level;
+            // Everything else the reload fetches is asked for HERE, in one batch with the rows, and used below them: the
+            // level's generator words, its exit slot and its constants depend on the level index alone.  Behind the
+            // goal-row stores, where they stood, each was a memory round trip of its own -- the compiler cannot rule out
+            // that env.goals overlaps the pool and kept the loads behind the stores, and the in-order counter then made
+            // each wait a full one (the stores' acknowledgements included).  Every lane loads, from a clamped index: a
+            // load inside a branch is waited for at the end of that branch.  (The empty asm keeps them in FRONT of the
+            // rows' loads: their address registers are free again before the rows' 2 x WS are taken.)
+            const u64 rng_pre = ((const u64 *)(env.pool_rng + level))[r2 & 3];
+            // (not the wrappers' spawner-free single-step kernel of 48-cell rows: with the exit slot held across the rows'
+            //  loads hipcc (ROCm 7.2) stops with "Illegal instruction detected: Operand has incorrect register class" in that
+            //  one instantiation; it keeps the slot's load behind the rows, as every kernel did before)
+            constexpr bool EXIT_PRE = !(WRAP && !SPAWN && ONE && W == 48);
+            int32_t exit_pre = -1;
+            if constexpr (EXIT_PRE) exit_pre = env.pool_exit_locs[(size_t)level * E + (r2 < E ? r2 : 0)];
+            const int table_pre = env.pool_scalars[level].table_idx;
+            const float spawn_pre = env.pool_scalars[level].spawn_prob;
+            asm volatile("" ::: "memory");
             // (round 6: where the batch keeps sl_env_batch.pool_ready the level comes as an episode starts on it --
             //  exits painted, its value in pool_scalars[l].ready -- and is neither scored nor repainted below)
             const u16 *pb = (ready_pool ? env.pool_ready : env.pool_board) + (size_t)level * HW, *pg = env.pool_goals + (size_t)level * HW;
@@ -2879,11 +2896,18 @@ __global__ __launch_bounds__(64 * WAVES,
                 }
                 if (Gm::ODD) imgs[a][Gm::cell(r, W - 1)] = (u16)tw[WS - 1];
             }
-            lut_base = (u32)env.pool_scalars[level].table_idx * (u32)SCORE_LUT_BYTES;
-            p = (double)env.pool_scalars[level].spawn_prob;
-            if (r2 < 4) rng_lds[4 * g + r2] = ((const u64 *)(env.pool_rng + level))[r2];
-            for (int k = r2; k < E; k += H)
-                env.exit_locs[(size_t)e * E + k] = env.pool_exit_locs[(size_t)level * E + k];
+            lut_base = (u32)table_pre * (u32)SCORE_LUT_BYTES;
+            p = (double)spawn_pre;
+            // (every row lane of the board writes the word it loaded, rows r, r + 4, ... the same value to the same place:
+            //  with the store inside `if (r2 < 4)` the compiler sinks the load into that branch, behind the stores again)
+            rng_lds[4 * g + (r2 & 3)] = rng_pre;
+            if (EXIT_PRE && r2 < E) env.exit_locs[(size_t)e * E + r2] = exit_pre;
+            if (r2 + (EXIT_PRE ? H : 0) < E) {           // (more exit slots than the board has rows; the level index is read again, not kept)
+                asm volatile("" ::: "memory");
+                const int level2 = box[gb].reset_level;
+                for (int k = r2 + (EXIT_PRE ? H : 0); k < E; k += H)
+                    env.exit_locs[(size_t)e * E + k] = env.pool_exit_locs[(size_t)level2 * E + k];
+            }
             if (!NOGOALS) *dirty_flag = 1;               // (any wave that changes its goals raises the flag)
             if (r2 == 0) box[gb].dirty = 1;              // (and the whole board is new)
         }
