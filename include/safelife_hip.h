@@ -1434,9 +1434,9 @@ typedef struct sl_history_entry { /* 32 bytes */
     int32_t env, level, episode_idx; /* the level slot PLAYED and the env's episode counter during the episode */
     int32_t length;               /* info['episode']['length']: frames 0 .. length - 1 (length - 2 with SL_HIST_NO_FINAL) */
     int32_t slot;
-    uint8_t success, times_up;
+    uint8_t success, times_up;    /* (several agents: success is a bit per agent, times_up their OR -- see _capture_multi) */
     uint8_t flags;                /* SL_HIST_LIVE | SL_HIST_NO_FINAL; 0: released */
-    uint8_t reserved;
+    uint8_t reserved;             /* 0 from slhip_history_capture; the agent count A from slhip_history_capture_multi */
 } sl_history_entry;
 
 typedef struct sl_episode_history { /* 112 bytes; every pointer is device memory */
@@ -1467,6 +1467,37 @@ int slhip_history_capture(const sl_episode_history *hist, const uint16_t *board,
  * takes one by the free order.  Counters and entries are not touched.  The same two launches. */
 int slhip_history_rewind(const sl_episode_history *hist, const uint16_t *goals, const sl_env_scalars *scalars,
                          const uint8_t *mask, void *stream);
+
+/* ---- episode histories of multi-agent envs (additive: one symbol; SL_ABI_VERSION stays where it is) -------------------------
+ * The reference's SafeLifeLogWrapper makes no difference between the env classes: it appends game.board after every step
+ * (safelife_logger.py:560-581), logs on np.all(done), and log_episode (:338-347) saves the stack whatever the agent count.
+ * Everything of the model above holds unchanged -- watched envs, slots, the free order, one goals plane per slot, the
+ * numbering, the queue cursor, the interval rule, `active` -- with `out` holding records [B, A], A = n_agents in
+ * 1 .. SL_MAX_AGENTS, and three things defined over the agents:
+ *   done        env e ends an episode on the step where ALL of out[e][0 .. A) have done != 0: the rule of
+ *               slhip_episode_log_harvest_multi and slhip_schedule_harvest_multi, and the step on which the multi-agent
+ *               kernel reloads the env and queues the episode.  The numbering ranks THESE flags over all B envs, masked by
+ *               `active`: a kept history's row is the row index of the multi-agent episode log.
+ *   frames      the reference appends a frame on every step until np.all(done), so an episode has as many frames as the
+ *               env took steps.  A live env writes frame scalars[e].num_steps - 1 (the multi-agent kernels count the env's
+ *               steps there and zero it on reload; they do not maintain scalars[e].episode_length, which the single-agent
+ *               pass reads).  An ended episode's length = max over a of out[e][a].episode_length: the agent that finished
+ *               last was active on every step (safelife_env.py:174-175), so the maximum is the step count, and it equals
+ *               the queue record's num_steps.
+ *   the entry   sl_history_entry keeps its 32 bytes.  length as above; success is a BIT MASK, bit a = (out[e][a].success
+ *               != 0) (at one agent: today's value); times_up = the OR over the agents (the same for all of them);
+ *               reserved = A (the single-agent pass keeps writing 0 there).
+ * Only the done byte of a record is looked at while the env's episode goes on: the other bytes of an agent that has left
+ * are read on the step where the last agent finishes, and by then the step has rewritten none of them.
+ * The last frame comes from the finished-episode queue exactly as above (the multi-agent step queues ONE entry per env
+ * episode, the board as the agents left it): the first j at or behind the cursor with (records[j].env - env_base,
+ * records[j].episode_idx) == (watch[i], cur_episode[i]).  slhip_history_rewind serves both env classes as it is: it reads
+ * scalars[e].level_idx, scalars[e].episode_idx and goals[e], which both kinds of kernels keep.
+ * The same two launches; the bookkeeping pass is the same body as the single-agent one, instantiated on a reader of A
+ * records per env (the done scan takes the nt * A records of a tile as one flat stream of unconditional loads). */
+int slhip_history_capture_multi(const sl_episode_history *hist, const uint16_t *board, const uint16_t *goals,
+                                const sl_env_scalars *scalars, const sl_step_out *out /* [B, A] */, int n_agents,
+                                const sl_episode_queue *queue, const uint8_t *active, void *stream);
 
 /* ---- the PPO update: minibatch deal, fused clipped loss and gradients (additive again: six symbols and one struct, nothing
  * existing changes; SL_ABI_VERSION stays where it is) --------------------------------------------------------------------------

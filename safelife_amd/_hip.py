@@ -42,7 +42,7 @@ EXPORTS = (
     "slhip_episode_log_harvest_multi", "slhip_episode_log_join_multi", "slhip_episode_log_summaries_multi",
     "slhip_episode_log_run_summary_multi",
     "slhip_episode_run_start", "slhip_episode_run_harvest", "slhip_episode_run_harvest_multi", "slhip_episode_run_tickets",
-    "slhip_history_capture", "slhip_history_rewind",
+    "slhip_history_capture", "slhip_history_rewind", "slhip_history_capture_multi",
     "slhip_ppo_workspace_bytes", "slhip_ppo_loss_forward", "slhip_ppo_loss_backward", "slhip_minibatch_obs",
     "slhip_minibatch_keys",
 )
@@ -406,6 +406,8 @@ def lib():
                                                 C.POINTER(LogWeights), _p]
         L.slhip_history_capture.argtypes = [C.POINTER(EpisodeHistory), _p, _p, _p, _p, C.POINTER(EpisodeQueue), _p, _p]
         L.slhip_history_rewind.argtypes = [C.POINTER(EpisodeHistory), _p, _p, _p, _p]
+        L.slhip_history_capture_multi.argtypes = [C.POINTER(EpisodeHistory), _p, _p, _p, _p, C.c_int, C.POINTER(EpisodeQueue),
+                                                  _p, _p]
         L.slhip_ppo_workspace_bytes.argtypes = [C.c_longlong]
         L.slhip_ppo_workspace_bytes.restype = C.c_size_t
         L.slhip_ppo_loss_forward.argtypes = [C.POINTER(PpoLoss), _p, _p, _p, _p]

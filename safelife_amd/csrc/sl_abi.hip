@@ -2132,20 +2132,37 @@ static int check_history(const sl_episode_history *h, const char *who) {
     return SL_OK;
 }
 
-int slhip_history_capture(const sl_episode_history *hist, const uint16_t *board, const uint16_t *goals,
-                          const sl_env_scalars *scalars, const sl_step_out *out, const sl_episode_queue *queue,
-                          const uint8_t *active, void *stream) {
-    if (int rc = check_history(hist, "history_capture")) return rc;
-    if (!board || !goals || !scalars || !out) return fail(SL_E_ARG, "history_capture: null board / goals / scalars / out");
+// n_agents == 0: records [B] (slhip_history_capture); 1 .. SL_MAX_AGENTS: records [B, A] (slhip_history_capture_multi)
+static int history_capture(const sl_episode_history *hist, const uint16_t *board, const uint16_t *goals,
+                           const sl_env_scalars *scalars, const sl_step_out *out, int n_agents, const sl_episode_queue *queue,
+                           const uint8_t *active, void *stream, const char *who) {
+    if (int rc = check_history(hist, who)) return rc;
+    if (!board || !goals || !scalars || !out) return fail(SL_E_ARG, std::string(who) + ": null board / goals / scalars / out");
     sl_episode_queue q;
     memset(&q, 0, sizeof(q));
     if (queue && queue->capacity > 0) {
         if (!queue->count || !queue->records || !queue->boards)
-            return fail(SL_E_ARG, "history_capture: a queue with slots needs count, records and boards");
+            return fail(SL_E_ARG, std::string(who) + ": a queue with slots needs count, records and boards");
         q = *queue;
     }
-    const hipError_t err = sl::launch_history_capture(*hist, board, goals, scalars, out, q, active, (hipStream_t)stream);
-    return err == hipSuccess ? SL_OK : hip_fail(err, "history_capture launch");
+    const hipError_t err =
+        n_agents ? sl::launch_history_capture_multi(*hist, board, goals, scalars, out, n_agents, q, active, (hipStream_t)stream)
+                 : sl::launch_history_capture(*hist, board, goals, scalars, out, q, active, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, (std::string(who) + " launch").c_str());
+}
+
+int slhip_history_capture(const sl_episode_history *hist, const uint16_t *board, const uint16_t *goals,
+                          const sl_env_scalars *scalars, const sl_step_out *out, const sl_episode_queue *queue,
+                          const uint8_t *active, void *stream) {
+    return history_capture(hist, board, goals, scalars, out, 0, queue, active, stream, "history_capture");
+}
+
+int slhip_history_capture_multi(const sl_episode_history *hist, const uint16_t *board, const uint16_t *goals,
+                                const sl_env_scalars *scalars, const sl_step_out *out, int n_agents,
+                                const sl_episode_queue *queue, const uint8_t *active, void *stream) {
+    if (n_agents < 1 || n_agents > SL_MAX_AGENTS)
+        return fail(SL_E_SHAPE, "history_capture_multi: n_agents outside 1..SL_MAX_AGENTS");
+    return history_capture(hist, board, goals, scalars, out, n_agents, queue, active, stream, "history_capture_multi");
 }
 
 int slhip_history_rewind(const sl_episode_history *hist, const uint16_t *goals, const sl_env_scalars *scalars,

@@ -156,6 +156,9 @@ hipError_t launch_episode_run_tickets(const sl_episode_run &run, const sl_episod
 hipError_t launch_history_capture(const sl_episode_history &h, const uint16_t *board, const uint16_t *goals,
                                   const sl_env_scalars *scalars, const sl_step_out *out, const sl_episode_queue &queue,
                                   const uint8_t *active, hipStream_t stream);
+hipError_t launch_history_capture_multi(const sl_episode_history &h, const uint16_t *board, const uint16_t *goals,
+                                        const sl_env_scalars *scalars, const sl_step_out *out, int n_agents,
+                                        const sl_episode_queue &queue, const uint8_t *active, hipStream_t stream);
 hipError_t launch_history_rewind(const sl_episode_history &h, const uint16_t *goals, const sl_env_scalars *scalars,
                                  const uint8_t *mask, hipStream_t stream);
 // the PPO update (sl_ppo.hip): the fused clipped loss and its gradients, a minibatch's observation rows, the deal's keys

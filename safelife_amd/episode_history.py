@@ -17,6 +17,10 @@ kernel changes; the model is in include/safelife_hip.h and restated in tests/epi
   which is why the env needs ``side_effects=``.
 * A slot keeps one goals plane: histories are for pools whose goals are static (all shipped levels).
 
+``MultiAgentEpisodeHistory`` is the same recorder for a ``SafeLifeMultiAgentVectorEnv`` (``slhip_history_capture_multi``: the
+same bookkeeping kernel reading A records per env): an episode ends where ALL agents are done, as the reference logs on
+``np.all(done)``; its length is the env's step count; ``success`` is a bit per agent.
+
 Video export stays with the caller: ``frames(i)`` hands over the RGB frames, ``save(i, path)`` the reference's ``.npz``.
 """
 import ctypes as C
@@ -46,27 +50,15 @@ def static_goals(pool_goals, torch, device):
     return ~((new & _SPAWNING) != 0).any(axis=(1, 2)) & (new == g).all(axis=(1, 2))
 
 
-class EpisodeHistory(object):
-    """
-    pool : LevelPool            single-agent, not refreshable, static goals
-    num_envs : int              of the env it will serve
-    watch : ints                the watched envs: distinct indices in 0..num_envs-1 (sorted here), at most 1024
-    slots : int                 frame slots, 1..1024
-    interval : int              the reference's ``video_interval``, >= 1
-    max_bytes : int             the slot memory the recorder may allocate (default 1 GiB)
-
-    Attach with ``SafeLifeVectorEnv(pool, ..., side_effects=dict(...), episode_history=h)``; a recorder serves one env.  Only
-    ``step()`` and ``reset()`` drive it.  ``entries()`` lists the kept histories in episode order; ``history(i)``, ``save(i,
-    path)`` and ``frames(i)`` read the i-th of that listing; ``release()`` hands slots back, and a watched env that found no
-    free slot picks one up where its next episode starts.
-    """
+class _EpisodeHistoryBase(object):
+    """What the two recorders share: the arguments, the device state, the rewind and the host side.  A subclass says which
+    pools it takes (``_check_agents``), what else it asks of its env (``_check_env``), where the env keeps what the capture
+    reads (``_env_state``) and which entry point captures (``_capture``)."""
 
     def __init__(self, pool, num_envs, watch, slots, interval=1, max_bytes=1 << 30):
         if not isinstance(pool, LevelPool):
             raise TypeError("pool must be a LevelPool")
-        if int(getattr(pool, "n_agents", 1)) > 1:
-            raise ValueError("episode histories serve a single-agent SafeLifeVectorEnv: this pool has %d agents per level "
-                             "(multi-agent histories are out of scope)" % pool.n_agents)
+        self._check_agents(int(getattr(pool, "n_agents", 1)))
         if getattr(pool, "refreshable", False):
             raise ValueError("episode histories refuse a refreshable pool: a slot keeps one goals plane and the level it "
                              "names, and a refresh replaces both under a recording episode")
@@ -97,7 +89,7 @@ class EpisodeHistory(object):
     def _check_env(self, pool, num_envs, time_limit, side_effects, torch, device):
         """Refuses an env this recorder cannot serve (called by the env before anything is allocated)."""
         if self.env is not None:
-            raise ValueError("this EpisodeHistory already serves an env")
+            raise ValueError("this %s already serves an env" % type(self).__name__)
         if pool is not self.pool:
             raise ValueError("the episode history was built for another pool")
         if int(num_envs) != self.num_envs:
@@ -113,6 +105,8 @@ class EpisodeHistory(object):
             H, W = pool.shape
             raise ValueError("the episode history's slots need %d bytes (slots %d * (time_limit %d + 1) * %d * %d * 2), "
                              "max_bytes allows %d" % (need, self.slots, time_limit, H, W, self.max_bytes))
+        if device is None:      # (the first thing here that needs one)
+            device = _hip.device()
         moving = np.flatnonzero(~static_goals(pool.arrays()["pool_goals"], torch, device))
         if len(moving):
             raise ValueError("episode histories need static goals: a slot keeps ONE goals plane, because the "
@@ -147,14 +141,13 @@ class EpisodeHistory(object):
         self._lib = _hip.lib()
         self.torch, self.env, self.time_limit = torch, env, T
         # (the env's state tensors live as long as it does, and a flush writes the fresh queue INTO struct.finished)
-        et = env.t
-        self._env_args = tuple(_hip.ptr(et[k]) for k in ("board", "goals", "scalars", "out")) + (C.byref(env.struct.finished),)
+        self._env_t, self._out, self._queue = self._env_state(env)
         self._rewind()
 
     def _rewind(self, mask=None):
         """After the envs (those with mask != 0) have been reset from outside the step: their episodes start over at frame
         0 on their new level; an env without a slot takes a free one."""
-        et = self.env.t
+        et = self._env_t
         _hip.check(self._lib.slhip_history_rewind(self._sref, _hip.ptr(et["goals"]), _hip.ptr(et["scalars"]), _hip.ptr(mask),
                                                   _hip.current_stream_ptr()))
 
@@ -162,7 +155,9 @@ class EpisodeHistory(object):
         """Two launches behind the step, in front of the episode run's and the log's harvests."""
         run = getattr(self.env, "episode_run", None)
         active = run.t["active"] if (run is not None and run._live) else None
-        rc = self._lib.slhip_history_capture(self._sref, *self._env_args, _hip.ptr(active), _hip.current_stream_ptr())
+        et = self._env_t
+        rc = self._capture(_hip.ptr(et["board"]), _hip.ptr(et["goals"]), _hip.ptr(et["scalars"]), _hip.ptr(self._out),
+                           self._queue, _hip.ptr(active), _hip.current_stream_ptr())
         if rc:
             _hip.check(rc)
 
@@ -174,7 +169,7 @@ class EpisodeHistory(object):
 
     def _need_state(self):
         if self.t is None:
-            raise ValueError("the episode history has no device state yet: hand it to SafeLifeVectorEnv(episode_history=...)")
+            raise ValueError("the episode history has no device state yet: hand it to %s(episode_history=...)" % self.ENV)
 
     def counters(self):
         """``kept`` (histories filed), ``missed`` (episodes the rule kept whose env owned no slot), ``incomplete`` (kept
@@ -238,3 +233,70 @@ class EpisodeHistory(object):
         self.t["slot_state"][slots] = _hip.HIST_SLOT_FREE
         self.t["entries"][slots] = 0
         return int(slots.numel())
+
+
+class EpisodeHistory(_EpisodeHistoryBase):
+    """
+    pool : LevelPool            single-agent, not refreshable, static goals
+    num_envs : int              of the env it will serve
+    watch : ints                the watched envs: distinct indices in 0..num_envs-1 (sorted here), at most 1024
+    slots : int                 frame slots, 1..1024
+    interval : int              the reference's ``video_interval``, >= 1
+    max_bytes : int             the slot memory the recorder may allocate (default 1 GiB)
+
+    Attach with ``SafeLifeVectorEnv(pool, ..., side_effects=dict(...), episode_history=h)``; a recorder serves one env.  Only
+    ``step()`` and ``reset()`` drive it.  ``entries()`` lists the kept histories in episode order; ``history(i)``, ``save(i,
+    path)`` and ``frames(i)`` read the i-th of that listing; ``release()`` hands slots back, and a watched env that found no
+    free slot picks one up where its next episode starts.
+    """
+    ENV = "SafeLifeVectorEnv"
+
+    def _check_agents(self, A):
+        if A > 1:
+            raise ValueError("episode histories serve a single-agent SafeLifeVectorEnv: this pool has %d agents per level "
+                             "(multi-agent histories are out of scope here: MultiAgentEpisodeHistory records them)" % A)
+
+    def _env_state(self, env):
+        return env.t, env.t["out"], C.byref(env.struct.finished)
+
+    def _capture(self, board, goals, scalars, out, queue, active, stream):
+        return self._lib.slhip_history_capture(self._sref, board, goals, scalars, out, queue, active, stream)
+
+
+class MultiAgentEpisodeHistory(_EpisodeHistoryBase):
+    """
+    The recorder of a ``SafeLifeMultiAgentVectorEnv``: the arguments, the listing and the readers of ``EpisodeHistory``, for
+    a ``LevelPool(levels, n_agents=A)`` with A >= 1.  The reference records these envs as it records the others -- a frame
+    after every step until ``np.all(done)`` -- so an episode ends on the step where the last agent finishes (the step on
+    which the env reloads and the ``MultiAgentEpisodeLog`` files its row: ``row`` is that row's index), ``length`` is the
+    number of steps the env took (the largest ``episode_length`` of its agents), ``times_up`` holds for all agents or none,
+    and ``success`` is a bit per agent: ``success(entry)`` unpacks it.  ``reserved`` carries A.
+
+    Attach with ``SafeLifeMultiAgentVectorEnv(pool, ..., side_effects=dict(...), episode_history=h)``; the env must reload
+    itself (``auto_reset=True``).
+    """
+    ENV = "SafeLifeMultiAgentVectorEnv"
+
+    def _check_agents(self, A):
+        if not 1 <= A <= _hip.SL_MAX_AGENTS:
+            raise ValueError("1..%d agents per level, this pool has %d" % (_hip.SL_MAX_AGENTS, A))
+        self.n_agents = A
+
+    def _check_env(self, pool, num_envs, time_limit, side_effects, torch, device, n_agents=None, auto_reset=True):
+        if n_agents is not None and int(n_agents) != self.n_agents:
+            raise ValueError("the episode history was built for %d agents per env, the env has %d" % (self.n_agents, n_agents))
+        if not auto_reset:
+            raise ValueError("an episode history needs auto_reset=True: an env that stays all-done would end an episode on "
+                             "every step where the reference saves the episode once")
+        _EpisodeHistoryBase._check_env(self, pool, num_envs, time_limit, side_effects, torch, device)
+
+    def _env_state(self, env):
+        return env.base.t, env.t["out"], C.byref(env.base.struct.finished)
+
+    def _capture(self, board, goals, scalars, out, queue, active, stream):
+        return self._lib.slhip_history_capture_multi(self._sref, board, goals, scalars, out, self.n_agents, queue, active,
+                                                     stream)
+
+    def success(self, entry):
+        """bool [A]: every agent's ``info['episode']['success']`` of a listed entry."""
+        return ((int(entry["success"]) >> np.arange(self.n_agents)) & 1).astype(bool)

@@ -49,6 +49,12 @@ class SafeLifeMultiAgentVectorEnv(object):
         ``**run.env_arguments()``; after ``run.start()`` one more launch per ``step()``, in front of the log's harvest, files
         the episodes whose agents are all done by ticket, retires the envs that have no ticket left and zeroes every
         record of a retired env.  Refuses ``level_schedule`` and ``wrappers``.  None: no launch and no allocation.
+    episode_history : episode_history.MultiAgentEpisodeHistory (built on this pool, for num_envs envs) or None
+        the board frames of selected episodes, the reference's ``SafeLifeLogWrapper`` history and ``SafeLifeLogger``'s
+        ``video_interval`` rule: two launches behind every ``step()``, in front of the run's and the log's harvests, copy the
+        watched envs' boards into frame slots; an episode ends where every agent is done.  Needs ``side_effects=`` (the last
+        frame comes from the finished-episode queue), ``auto_reset=True`` and a pool with static goals.  None: no launch and
+        no allocation.
 
     ``reset()`` -> obs;  ``step(actions)`` -> (obs, reward, done, info) with
         actions  int   [B, A]   0..8 (an agent that is done takes 0: training/base_algo.py:216-219)
@@ -63,7 +69,8 @@ class SafeLifeMultiAgentVectorEnv(object):
     def __init__(self, pool, num_envs, *, time_limit=1000, remove_white_goals=True, view_shape=(15, 15),
                  output_channels=tuple(range(16)) + (25, 26, 27), auto_reset=True, first_level=None, level_stride=1,
                  env_offset=0, with_obs=True, points_on_level_exit=1, episode_streams=True, wrappers=None,
-                 side_effects=None, policy_layout=None, level_schedule=None, episode_log=None, episode_run=None):
+                 side_effects=None, policy_layout=None, level_schedule=None, episode_log=None, episode_run=None,
+                 episode_history=None):
         import torch
         if not isinstance(pool, LevelPool) or getattr(pool, "n_agents", 1) < 1:
             raise TypeError("pool must be a LevelPool")
@@ -76,6 +83,11 @@ class SafeLifeMultiAgentVectorEnv(object):
         if episode_run is not None:         # (refused before anything is allocated)
             episode_run._check_env(pool, num_envs, A, auto_reset, first_level, level_stride, env_offset, level_schedule,
                                    wrappers)
+        if episode_history is not None:     # (refused before anything is allocated)
+            if not hasattr(episode_history, "n_agents"):
+                raise ValueError("a multi-agent env takes an episode_history.MultiAgentEpisodeHistory")
+            episode_history._check_env(pool, num_envs, time_limit, side_effects, torch, None, n_agents=A,
+                                       auto_reset=auto_reset)
         if level_schedule is not None:
             level_schedule._check_env(pool, A)
             if first_level is None:
@@ -87,7 +99,7 @@ class SafeLifeMultiAgentVectorEnv(object):
                                              with_obs=False, points_on_level_exit=points_on_level_exit,
                                              episode_streams=episode_streams, wrappers=wrappers, side_effects=side_effects)
         self.torch, self.pool, self.device = torch, pool, base.device
-        self.num_envs, self.n_agents = int(num_envs), A
+        self.num_envs, self.n_agents, self.time_limit = int(num_envs), A, base.time_limit
         B = self.num_envs
         base.struct.goal_cache = None       # (the multi-agent kernels keep no goal words: nothing to drop per launch)
         self.view_shape, self.output_channels = base.view_shape, base.output_channels
@@ -142,6 +154,11 @@ class SafeLifeMultiAgentVectorEnv(object):
         if episode_run is not None:         # one launch behind every step() of a started run, in front of the log's
             episode_run._attach(self)
             base.episode_run = episode_run  # (... and a run)
+        self.episode_history = episode_history
+        if episode_history is not None:     # two launches behind every step(): the watched envs' frames
+            episode_history._attach(self)
+            # (... and a recorder; the flush's hook that tells it of a fresh queue hangs on this too)
+            base.episode_history = episode_history
 
     def _setup_extras(self, wrappers, side_effects, policy_layout):
         torch, t, base, dev = self.torch, self.t, self.base, self.device
@@ -201,6 +218,8 @@ class SafeLifeMultiAgentVectorEnv(object):
             sched._rewind(mk)
         if self.episode_log is not None:
             self.episode_log._rewind(mk)
+        if self.episode_history is not None:
+            self.episode_history._rewind(mk)
         if mk is not None:
             self.torch.cuda.current_stream().synchronize()      # (the mask tensor is the call's own)
         return self.obs
@@ -221,6 +240,8 @@ class SafeLifeMultiAgentVectorEnv(object):
             _hip.check(self._lib.slhip_env_step_multi(self.base._sref, self._mref, a.data_ptr(), _hip.current_stream_ptr()))
         if sched is not None:
             sched._after_step()
+        if self.episode_history is not None:
+            self.episode_history._after_step()
         if self.episode_run is not None:
             self.episode_run._after_step()
         if self.episode_log is not None:
