@@ -1573,6 +1573,77 @@ int slhip_minibatch_obs(const void *obs, long long obs_bytes, long long N, const
  * slhip_sample_actions' construction with the epoch as the counter.  A minibatch deal is the stable argsort of the keys. */
 int slhip_minibatch_keys(long long N, unsigned long long seed, unsigned long long epoch, unsigned long long *keys, void *stream);
 
+/* ---- the DQN update: fused TD loss and gradients (additive again: three symbols and one struct, nothing existing changes;
+ * SL_ABI_VERSION stays where it is) ------------------------------------------------------------------------------------------
+ * What the reference's DQN.optimize does with a sample after the two model calls (training/dqn.py:152-157) and what it reports
+ * (:165-170).  The struct lives on the HOST; every pointer inside is a device pointer the caller owns.
+ *
+ * The three per-row scalars come in one of two forms (`source`):
+ *   SL_DQN_FROM_RING    action int32, reward float64, done uint8: the storage of sl_replay's ring, read in place
+ *   SL_DQN_FROM_BATCH   action int64, reward float32, done float32: what slhip_replay_gather wrote
+ * Per minibatch row i (r = index ? index[i] : i the source row behind it, a = action[r]; f32(x) = x rounded to float32; every
+ * operation below is a separate float32 operation in this order, nothing is contracted into an FMA):
+ *   rew_i  = f32(reward[r])                        ring form: the float64 n-step sum rounded ONCE, as slhip_replay_gather does
+ *   nd_i   = 1 - f32(done[r])
+ *   disc_i = f32(discount) * nd_i                  discount: gamma ** multi_step, computed by the caller in double
+ *   m_i    = max over k of next_q_values[i][k]     torch.max's value: NaN if any element is NaN
+ *   exp_i  = rew_i + disc_i * m_i                  the product rounded, then the sum rounded
+ *   td_i   = q_values[i][a] - exp_i
+ * and over the minibatch, in float64 (deterministic sums of the float32 terms: a fixed tree per workgroup of 256 rows, the
+ * workgroups in index order; a row's elements are added in index order):
+ *   loss          = sum(td_i * td_i) / n           each square a float32 product
+ *   q_model_mean  = sum of the n * n_actions elements of q_values / (n * n_actions)
+ *   q_model_max   = sum over i of (max over k of q_values[i][k]) / n
+ *   q_target_mean = sum of the n * n_actions elements of next_q_values / (n * n_actions)
+ *   q_target_max  = sum(m_i) / n
+ * An index outside [0, N) raises SL_DQN_BAD_INDEX in *status, an action outside [0, n_actions) SL_DQN_BAD_ACTION; such a row
+ * reads nothing through the bad value, has td_i = 0, adds zero to the loss sum and to q_target_max (n stays the divisor) and gets
+ * zero gradients.  q_model_mean, q_model_max and q_target_mean depend on neither index nor action and count every row. */
+#define SL_DQN_BAD_ACTION 1
+#define SL_DQN_BAD_INDEX 2
+#define SL_DQN_FROM_RING 0
+#define SL_DQN_FROM_BATCH 1
+#define SL_DQN_SUMS 8               /* doubles in sums_out */
+#define SL_DQN_SUM_LOSS 0
+#define SL_DQN_SUM_Q_MODEL_MEAN 1
+#define SL_DQN_SUM_Q_MODEL_MAX 2
+#define SL_DQN_SUM_Q_TARGET_MEAN 3
+#define SL_DQN_SUM_Q_TARGET_MAX 4
+#define SL_DQN_SUM_N 5              /* n */
+#define SL_DQN_SUM_RESERVED 6       /* zero */
+#define SL_DQN_SUM_LOSS_F32 7       /* NOT a double: the slot's first four bytes hold loss rounded to float32, the rest zero */
+typedef struct sl_dqn_loss {        /* 88 bytes */
+    long long n;                    /* rows of the minibatch: of q_values, next_q_values and index; >= 1 */
+    long long N;                    /* rows of the source: of action, reward and done; >= 1 */
+    int32_t n_actions;              /* 2 .. 32 */
+    int32_t source;                 /* SL_DQN_FROM_RING or SL_DQN_FROM_BATCH */
+    double discount;                /* gamma ** multi_step */
+    const float *q_values;          /* [n, n_actions] the training model's Q-values for the minibatch's observations */
+    const float *next_q_values;     /* [n, n_actions] the target model's for its next observations (no gradient) */
+    const void *action;             /* [N] int32 (ring) or int64 (batch) */
+    const void *reward;             /* [N] float64 (ring) or float32 (batch) */
+    const void *done;               /* [N] uint8 (ring) or float32 (batch) */
+    const long long *index;         /* [n] source row of every minibatch row, or NULL: row i is source row i and n == N */
+    long long *status;              /* one device word, zeroed by the caller; the kernels only ever set bits (SL_DQN_*) */
+} sl_dqn_loss;
+
+/* bytes of `workspace` for a minibatch of n rows (five doubles per workgroup of 256 rows); 8-byte aligned */
+size_t slhip_dqn_workspace_bytes(long long n);
+
+/* td_out float32 [n]: td_i;  sums_out double [SL_DQN_SUMS], 8-byte aligned: the SL_DQN_SUM_* above.  The row pass and a
+ * one-workgroup finish: two launches, or ONE when the minibatch fits the row pass's single workgroup (n <= 256; the reference's
+ * batch of 96 rows does) -- the workgroup then finishes its own sums, to the same bits. */
+int slhip_dqn_loss_forward(const sl_dqn_loss *loss, float *td_out, double *sums_out, void *workspace, void *stream);
+
+/* d_q float32 [n, n_actions], every element written: the gradient torch's autograd gives the expression above for
+ *   *grad_loss * loss + sum_i grad_td[i] * td_i              (grad_loss: a device float32; grad_td: [n] or NULL)
+ * with respect to q_values (next_q_values is detached in the reference):
+ *   d_q[i][k] = (*grad_loss / f32(n)) * (2 * td_i) (+ grad_td[i]) at k = a, and 0 elsewhere
+ * -- mean's backward divides by f32(n), pow's multiplies by 2 * td, gather's scatters.  Reads td (what slhip_dqn_loss_forward
+ * wrote for the same *loss), the actions through index, and nothing else.  One launch. */
+int slhip_dqn_loss_backward(const sl_dqn_loss *loss, const float *grad_loss, const float *grad_td, const float *td,
+                            float *d_q, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

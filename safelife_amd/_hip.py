@@ -45,11 +45,17 @@ EXPORTS = (
     "slhip_history_capture", "slhip_history_rewind", "slhip_history_capture_multi",
     "slhip_ppo_workspace_bytes", "slhip_ppo_loss_forward", "slhip_ppo_loss_backward", "slhip_minibatch_obs",
     "slhip_minibatch_keys",
+    "slhip_dqn_workspace_bytes", "slhip_dqn_loss_forward", "slhip_dqn_loss_backward",
 )
 PPO_BAD_ACTION, PPO_BAD_INDEX = 1, 2
 #: sums_out of slhip_ppo_loss_forward: the doubles' names in order; slot PPO_SUM_LOSS_F32 holds a float32, not a double
 PPO_SUMS = ("policy", "value", "entropy", "entropy_term", "loss", "flag", "n")
 PPO_SUM_LOSS_F32 = 7
+DQN_BAD_ACTION, DQN_BAD_INDEX = 1, 2
+DQN_FROM_RING, DQN_FROM_BATCH = 0, 1
+#: sums_out of slhip_dqn_loss_forward: the doubles' names in order; slot DQN_SUM_LOSS_F32 holds a float32, not a double
+DQN_SUMS = ("loss", "q_model_mean", "q_model_max", "q_target_mean", "q_target_max", "n", "reserved")
+DQN_SUM_LOSS_F32 = 7
 HIST_LIVE, HIST_NO_FINAL = 1, 2
 HIST_SLOT_FREE, HIST_SLOT_ENV, HIST_SLOT_ENTRY = 0, 1, 2
 HIST_MAX_WATCH, HIST_MAX_SLOTS, HIST_ORDER_WORDS = 1024, 1024, 8
@@ -254,6 +260,13 @@ class PpoLoss(C.Structure):
                                              "advantages", "rows", "status")])
 
 
+class DqnLoss(C.Structure):
+    """struct sl_dqn_loss (88 bytes)"""
+    _fields_ = ([("n", C.c_longlong), ("N", C.c_longlong), ("n_actions", C.c_int32), ("source", C.c_int32),
+                 ("discount", C.c_double)]
+                + [(n, C.c_void_p) for n in ("q_values", "next_q_values", "action", "reward", "done", "index", "status")])
+
+
 class EpisodeRun(C.Structure):
     """struct sl_episode_run (80 bytes)"""
     _fields_ = ([(n, C.c_int32) for n in ("B", "G", "env_offset", "N", "L", "n_agents")]
@@ -414,6 +427,10 @@ def lib():
         L.slhip_ppo_loss_backward.argtypes = [C.POINTER(PpoLoss), _p, _p, _p, _p, _p, _p]
         L.slhip_minibatch_obs.argtypes = [_p, C.c_longlong, C.c_longlong, _p, C.c_longlong, _p, C.c_int, _p, _p]
         L.slhip_minibatch_keys.argtypes = [C.c_longlong, C.c_ulonglong, C.c_ulonglong, _p, _p]
+        L.slhip_dqn_workspace_bytes.argtypes = [C.c_longlong]
+        L.slhip_dqn_workspace_bytes.restype = C.c_size_t
+        L.slhip_dqn_loss_forward.argtypes = [C.POINTER(DqnLoss), _p, _p, _p, _p]
+        L.slhip_dqn_loss_backward.argtypes = [C.POINTER(DqnLoss), _p, _p, _p, _p, _p]
         L.slhip_obs_to_policy.argtypes = [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]
         L.slhip_gather_unique_id.argtypes = [_p]
         L.slhip_gather_init.argtypes = [_p, C.c_int, C.c_int, C.POINTER(_p)]

@@ -2221,4 +2221,34 @@ int slhip_minibatch_keys(long long N, unsigned long long seed, unsigned long lon
     return err == hipSuccess ? SL_OK : hip_fail(err, "minibatch_keys launch");
 }
 
+static int check_dqn_loss(const sl_dqn_loss *p) {
+    if (!p) return fail(SL_E_ARG, "dqn_loss: null description");
+    if (p->n < 1 || p->N < 1) return fail(SL_E_ARG, "dqn_loss: n and N must be at least 1");
+    if (p->n_actions < 2 || p->n_actions > 32) return fail(SL_E_ARG, "dqn_loss: n_actions outside 2..32");
+    if (p->source != SL_DQN_FROM_RING && p->source != SL_DQN_FROM_BATCH)
+        return fail(SL_E_ARG, "dqn_loss: source is neither SL_DQN_FROM_RING nor SL_DQN_FROM_BATCH");
+    if (!p->index && p->n != p->N) return fail(SL_E_ARG, "dqn_loss: without index n must equal N");
+    if (!p->q_values || !p->next_q_values || !p->action || !p->reward || !p->done || !p->status)
+        return fail(SL_E_ARG, "dqn_loss: null pointer in the description");
+    return SL_OK;
+}
+
+size_t slhip_dqn_workspace_bytes(long long n) { return n < 1 ? 0 : sl::dqn_workspace_bytes(n); }
+
+int slhip_dqn_loss_forward(const sl_dqn_loss *loss, float *td_out, double *sums_out, void *workspace, void *stream) {
+    if (int rc = check_dqn_loss(loss)) return rc;
+    if (!td_out || !sums_out || !workspace) return fail(SL_E_ARG, "dqn_loss_forward: null pointer");
+    if (((uintptr_t)sums_out | (uintptr_t)workspace) & 7) return fail(SL_E_ARG, "dqn_loss_forward: sums_out / workspace not 8-byte aligned");
+    const hipError_t err = sl::launch_dqn_loss_forward(*loss, td_out, sums_out, workspace, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "dqn_loss_forward launch");
+}
+
+int slhip_dqn_loss_backward(const sl_dqn_loss *loss, const float *grad_loss, const float *grad_td, const float *td,
+                            float *d_q, void *stream) {
+    if (int rc = check_dqn_loss(loss)) return rc;
+    if (!grad_loss || !td || !d_q) return fail(SL_E_ARG, "dqn_loss_backward: null pointer");
+    const hipError_t err = sl::launch_dqn_loss_backward(*loss, grad_loss, grad_td, td, d_q, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "dqn_loss_backward launch");
+}
+
 }  // extern "C"

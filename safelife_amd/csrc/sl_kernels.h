@@ -171,6 +171,11 @@ hipError_t launch_minibatch_obs(const void *obs, long long obs_bytes, long long 
                                 void *out, int out_float32, long long *status, hipStream_t stream);
 hipError_t launch_minibatch_keys(long long N, unsigned long long seed, unsigned long long epoch, unsigned long long *keys,
                                  hipStream_t stream);
+// the DQN update (sl_dqn.hip): the fused TD loss with the report scalars, and its gradient
+size_t dqn_workspace_bytes(long long n);
+hipError_t launch_dqn_loss_forward(const sl_dqn_loss &p, float *td_out, double *sums_out, void *workspace, hipStream_t stream);
+hipError_t launch_dqn_loss_backward(const sl_dqn_loss &p, const float *grad_loss, const float *grad_td, const float *td,
+                                    float *d_q, hipStream_t stream);
 // envs [e_first, e_first + e_count) of the batch; actions / reward_t / done_t are indexed [t * tstride + e]
 // with the env's index in the whole batch
 // (sl_aql.hip dispatches the same kernel from queues of the library's own: PreparedStep below)
