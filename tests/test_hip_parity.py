@@ -119,7 +119,7 @@ def test_side_effect_occupancy_tensors(sp, fixture):
                                      ((100, 100), 6), ((128, 128), 2),
                                      ((8, 8), 70), ((12, 12), 45), ((16, 16), 37), ((24, 24), 19), ((30, 30), 21),
                                      ((32, 32), 18), ((40, 40), 9), ((48, 48), 7)])
-@pytest.mark.parametrize("kind", [0, 1, 2])
+@pytest.mark.parametrize("kind", [0, 1, 2, 3])
 def test_advance_board_vs_oracle(sp, shape, B, kind):
     rng = np.random.default_rng(hash((shape, kind)) % 2**31)
     boards = util.random_boards(rng, B, shape[0], shape[1], kind)
@@ -138,7 +138,7 @@ def test_advance_board_vs_oracle(sp, shape, B, kind):
                                             ((9, 31), 6, 60), ((25, 25), 3, 0), ((8, 8), 40, 50), ((12, 12), 11, 50),
                                             ((16, 16), 9, 50), ((24, 24), 5, 50), ((30, 30), 5, 50), ((32, 32), 6, 50),
                                             ((40, 40), 5, 50), ((48, 48), 3, 50)])
-@pytest.mark.parametrize("kind", [0, 1])
+@pytest.mark.parametrize("kind", [0, 1, 2, 3])
 def test_life_occupancy_vs_oracle(sp, shape, B, n_step, kind):
     import torch
     rng = np.random.default_rng(hash((shape, kind, n_step)) % 2**31)

@@ -46,7 +46,7 @@ SHAPES = [(25, 25), (26, 26), (8, 8), (10, 10), (12, 12), (15, 15), (16, 16), (2
 
 
 @pytest.mark.parametrize("H,W", SHAPES)
-@pytest.mark.parametrize("kind", [0, 1, 2])
+@pytest.mark.parametrize("kind", [0, 1, 2, 3])
 def test_plane_step_matches_oracle(sim, tmp_path, H, W, kind):
     rng = np.random.default_rng(1000 * H + 10 * W + kind)
     for spawn in (False, True):

@@ -30,6 +30,11 @@ def random_boards(rng, B, H, W, kind=0):
             for _ in range(4):
                 b[k, rng.integers(0, H), rng.integers(0, W)] = 152 | (int(rng.integers(0, 8)) << 9)
         return b
+    if kind == 3:       # the rule soup: uniform 16-bit cells whose bits 4-7 (frozen, preserving, inhibiting, spawning) are
+        b = rng.integers(0, 65536, (B, H, W)).astype(np.uint16) & np.uint16(0xFF0F)    # each set with probability 1/16:
+        for bit in (4, 5, 6, 7):                                   # the boards keep moving (kind 2 is nearly static)
+            b |= ((rng.random((B, H, W)) < 1 / 16).astype(np.uint16) << np.uint16(bit))
+        return b
     return rng.integers(0, 65536, (B, H, W)).astype(np.uint16)
 
 
