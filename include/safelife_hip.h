@@ -1573,6 +1573,42 @@ int slhip_minibatch_obs(const void *obs, long long obs_bytes, long long N, const
  * slhip_sample_actions' construction with the epoch as the counter.  A minibatch deal is the stable argsort of the keys. */
 int slhip_minibatch_keys(long long N, unsigned long long seed, unsigned long long epoch, unsigned long long *keys, void *stream);
 
+/* ---- the PPO report: loss / entropy / values / advantages over a WHOLE batch, evaluated chunk by chunk (additive again: three
+ * symbols, nothing existing changes; SL_ABI_VERSION stays where it is) ------------------------------------------------------
+ * What the reference's PPO.train logs (training/ppo.py:199-205): calculate_loss on the whole batch, its loss, the mean entropy,
+ * and the means of batch.values and batch.advantages.  The reference calls the model on the whole batch at once; here the
+ * caller calls it on chunks of the batch and hands every chunk's outputs to slhip_ppo_report_rows, then calls
+ * slhip_ppo_report_finish once.  The loss clips the entropy bonus at the BATCH's mean entropy, so chunk losses cannot be
+ * averaged: the row pass leaves float64 partial sums, one set per 256 batch rows, each at its place in the whole batch, and
+ * the finish adds them in index order.  The result is the same, bit for bit, however the batch was cut into chunks, and its
+ * first seven doubles are the sums_out slhip_ppo_loss_forward writes for the whole batch in one call (rows == NULL). */
+#define SL_PPO_REPORT_PARTIALS 5     /* doubles per 256 rows in the workspace: policy, value, entropy, old_values, advantages */
+#define SL_PPO_REPORT_DOUBLES 11     /* doubles in `out`; slots 0 .. 6 are SL_PPO_SUM_POLICY .. SL_PPO_SUM_N */
+#define SL_PPO_REPORT_VALUES 7       /* mean of old_values (batch.values) */
+#define SL_PPO_REPORT_ADVANTAGES 8   /* mean of advantages */
+#define SL_PPO_REPORT_F32 9          /* NOT doubles: slots 9 and 10 hold four float32, the scalars as the reference logs them */
+#define SL_PPO_REPORT_F32_LOSS 0
+#define SL_PPO_REPORT_F32_ENTROPY 1
+#define SL_PPO_REPORT_F32_VALUES 2
+#define SL_PPO_REPORT_F32_ADVANTAGES 3
+
+/* bytes of the report's workspace for a batch of N rows (five doubles per 256 rows); 8-byte aligned */
+size_t slhip_ppo_report_workspace_bytes(long long N);
+
+/* Rows [first_row, first_row + loss->n) of a batch of loss->N rows: loss->values [n] and loss->policy [n, n_actions] are the
+ * model's outputs for THIS CHUNK, the five per-row scalars are read at batch row first_row + i, loss->rows is not looked at.
+ * first_row must be a multiple of 256 with first_row + n <= N, and n a multiple of 256 unless the chunk ends the batch:
+ * anything else returns SL_E_ARG and writes nothing.  Workgroup b writes SL_PPO_REPORT_PARTIALS doubles at
+ * partial[(first_row / 256 + b) * SL_PPO_REPORT_PARTIALS]; the first three are the very numbers slhip_ppo_loss_forward's row pass
+ * leaves for the same rows.  A row whose action is outside [0, n_actions) raises SL_PPO_BAD_ACTION in *status and adds zero to
+ * all five.  No per-row output, no gradient.  One launch. */
+int slhip_ppo_report_rows(const sl_ppo_loss *loss, long long first_row, double *partial, void *stream);
+
+/* After the row pass has covered every row of the batch: `blocks` = ceil(N / 256) sets of partials -> out double
+ * [SL_PPO_REPORT_DOUBLES].  The divisor of every mean is loss->N; only N and the five hyper-parameters of *loss are read.  One
+ * workgroup. */
+int slhip_ppo_report_finish(const sl_ppo_loss *loss, const double *partial, long long blocks, double *out, void *stream);
+
 /* ---- the DQN update: fused TD loss and gradients (additive again: three symbols and one struct, nothing existing changes;
  * SL_ABI_VERSION stays where it is) ------------------------------------------------------------------------------------------
  * What the reference's DQN.optimize does with a sample after the two model calls (training/dqn.py:152-157) and what it reports

@@ -45,12 +45,17 @@ EXPORTS = (
     "slhip_history_capture", "slhip_history_rewind", "slhip_history_capture_multi",
     "slhip_ppo_workspace_bytes", "slhip_ppo_loss_forward", "slhip_ppo_loss_backward", "slhip_minibatch_obs",
     "slhip_minibatch_keys",
+    "slhip_ppo_report_workspace_bytes", "slhip_ppo_report_rows", "slhip_ppo_report_finish",
     "slhip_dqn_workspace_bytes", "slhip_dqn_loss_forward", "slhip_dqn_loss_backward",
 )
 PPO_BAD_ACTION, PPO_BAD_INDEX = 1, 2
 #: sums_out of slhip_ppo_loss_forward: the doubles' names in order; slot PPO_SUM_LOSS_F32 holds a float32, not a double
 PPO_SUMS = ("policy", "value", "entropy", "entropy_term", "loss", "flag", "n")
 PPO_SUM_LOSS_F32 = 7
+#: out of slhip_ppo_report_finish: PPO_SUMS, then these two doubles, then four float32 in slots PPO_REPORT_F32 and the next
+PPO_REPORT_PARTIALS, PPO_REPORT_DOUBLES = 5, 11
+PPO_REPORT_VALUES, PPO_REPORT_ADVANTAGES, PPO_REPORT_F32 = 7, 8, 9
+PPO_REPORT_SCALARS = ("loss", "entropy", "values", "advantages")       # the float32 in order
 DQN_BAD_ACTION, DQN_BAD_INDEX = 1, 2
 DQN_FROM_RING, DQN_FROM_BATCH = 0, 1
 #: sums_out of slhip_dqn_loss_forward: the doubles' names in order; slot DQN_SUM_LOSS_F32 holds a float32, not a double
@@ -427,6 +432,10 @@ def lib():
         L.slhip_ppo_loss_backward.argtypes = [C.POINTER(PpoLoss), _p, _p, _p, _p, _p, _p]
         L.slhip_minibatch_obs.argtypes = [_p, C.c_longlong, C.c_longlong, _p, C.c_longlong, _p, C.c_int, _p, _p]
         L.slhip_minibatch_keys.argtypes = [C.c_longlong, C.c_ulonglong, C.c_ulonglong, _p, _p]
+        L.slhip_ppo_report_workspace_bytes.argtypes = [C.c_longlong]
+        L.slhip_ppo_report_workspace_bytes.restype = C.c_size_t
+        L.slhip_ppo_report_rows.argtypes = [C.POINTER(PpoLoss), C.c_longlong, _p, _p]
+        L.slhip_ppo_report_finish.argtypes = [C.POINTER(PpoLoss), _p, C.c_longlong, _p, _p]
         L.slhip_dqn_workspace_bytes.argtypes = [C.c_longlong]
         L.slhip_dqn_workspace_bytes.restype = C.c_size_t
         L.slhip_dqn_loss_forward.argtypes = [C.POINTER(DqnLoss), _p, _p, _p, _p]

@@ -2203,6 +2203,34 @@ int slhip_ppo_loss_backward(const sl_ppo_loss *loss, const float *grad_loss, con
     return err == hipSuccess ? SL_OK : hip_fail(err, "ppo_loss_backward launch");
 }
 
+size_t slhip_ppo_report_workspace_bytes(long long N) { return N < 1 ? 0 : sl::ppo_report_workspace_bytes(N); }
+
+int slhip_ppo_report_rows(const sl_ppo_loss *loss, long long first_row, double *partial, void *stream) {
+    const sl_ppo_loss *p = loss;
+    if (!p) return fail(SL_E_ARG, "ppo_report_rows: null description");
+    if (p->n < 1 || p->N < 1) return fail(SL_E_ARG, "ppo_report_rows: n and N must be at least 1");
+    if (p->n_actions < 2 || p->n_actions > 32) return fail(SL_E_ARG, "ppo_report_rows: n_actions outside 2..32");
+    if (first_row < 0 || first_row % 256) return fail(SL_E_ARG, "ppo_report_rows: first_row must be a multiple of 256");
+    if (p->n > p->N || first_row > p->N - p->n) return fail(SL_E_ARG, "ppo_report_rows: the chunk ends beyond the batch");
+    if (p->n % 256 && first_row + p->n != p->N)
+        return fail(SL_E_ARG, "ppo_report_rows: a chunk that does not end the batch must hold a multiple of 256 rows");
+    if (!p->values || !p->policy || !p->actions || !p->action_prob || !p->old_values || !p->returns || !p->advantages ||
+        !p->status || !partial)
+        return fail(SL_E_ARG, "ppo_report_rows: null pointer");
+    if ((uintptr_t)partial & 7) return fail(SL_E_ARG, "ppo_report_rows: partial not 8-byte aligned");
+    const hipError_t err = sl::launch_ppo_report_rows(*p, first_row, partial, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "ppo_report_rows launch");
+}
+
+int slhip_ppo_report_finish(const sl_ppo_loss *loss, const double *partial, long long blocks, double *out, void *stream) {
+    if (!loss || !partial || !out) return fail(SL_E_ARG, "ppo_report_finish: null pointer");
+    if (loss->N < 1 || blocks != (loss->N + 255) / 256)
+        return fail(SL_E_ARG, "ppo_report_finish: blocks must be ceil(N / 256) of a batch of N >= 1 rows");
+    if (((uintptr_t)partial | (uintptr_t)out) & 7) return fail(SL_E_ARG, "ppo_report_finish: partial / out not 8-byte aligned");
+    const hipError_t err = sl::launch_ppo_report_finish(*loss, partial, blocks, out, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "ppo_report_finish launch");
+}
+
 int slhip_minibatch_obs(const void *obs, long long obs_bytes, long long N, const long long *rows, long long n, void *out,
                         int out_float32, long long *status, void *stream) {
     if (obs_bytes < 1 || N < 1 || n < 0) return fail(SL_E_ARG, "minibatch_obs: obs_bytes and N must be at least 1, n at least 0");

@@ -167,6 +167,10 @@ hipError_t launch_ppo_loss_forward(const sl_ppo_loss &p, float *entropy_out, dou
                                    hipStream_t stream);
 hipError_t launch_ppo_loss_backward(const sl_ppo_loss &p, const float *grad_loss, const float *grad_entropy,
                                     const double *sums, float *d_values, float *d_policy, hipStream_t stream);
+size_t ppo_report_workspace_bytes(long long N);
+hipError_t launch_ppo_report_rows(const sl_ppo_loss &p, long long first_row, double *partial, hipStream_t stream);
+hipError_t launch_ppo_report_finish(const sl_ppo_loss &p, const double *partial, long long blocks, double *out,
+                                    hipStream_t stream);
 hipError_t launch_minibatch_obs(const void *obs, long long obs_bytes, long long N, const long long *rows, long long n,
                                 void *out, int out_float32, long long *status, hipStream_t stream);
 hipError_t launch_minibatch_keys(long long N, unsigned long long seed, unsigned long long epoch, unsigned long long *keys,

@@ -20,6 +20,10 @@
 //                   workspace: a butterfly over the wavefront, then the waves in order -- a fixed tree, no atomics.
 //   k_ppo_finish    one workgroup: the partials through LDS, added in index order by one lane per quantity; the means,
 //                   the entropy term, the total, the flag "the entropy bonus has a gradient" and n.
+//   k_ppo_report_rows / k_ppo_report_finish   the report of PPO.train (training/ppo.py:199-205) over a batch too large for
+//                   one model call: k_ppo_rows' per-row body and tree on one chunk of the batch at a time, five partials
+//                   per workgroup (the three terms, old_values, advantages) at the workgroup's place in the whole batch,
+//                   then one workgroup for the means -- the same bits however the batch was cut.  No gradient.
 //   k_ppo_backward  one pass, the same tile: the gradients torch's autograd gives the expression above (a clamp passes
 //                   the gradient at equality, a maximum halves it on a tie, sign(0) = 0, the bonus stops above the clip),
 //                   recomputed from the inputs and the flag, written into the tile and stored from there with
@@ -84,6 +88,45 @@ __device__ __forceinline__ double wave_sum(double x) {
     return x;
 }
 
+// The three float32 terms of minibatch row i (batch row r, action a, its policy row `pi` in LDS): the one per-row body of
+// the loss pass and the report pass, so both give the same bits for the same row.
+__device__ __forceinline__ void ppo_row_terms(const sl_ppo_loss &p, long long i, long long r, int a, const float *pi,
+                                              float &pol, float &val, float &ent) {
+    const int A = p.n_actions;
+    for (int k = 0; k < A; ++k) {
+        const float pk = pi[k];
+        const float t = (-pk) * logf(pk + 1e-12f);
+        ent = k ? ent + t : t;
+    }
+    const float adv = p.advantages[r], old_p = p.action_prob[r], old_v = p.old_values[r], ret = p.returns[r];
+    const float v = p.values[i];
+    const float lo = -(float)p.eps_policy, ev = (float)p.eps_value;
+    const float pd = sign_of(adv) * (1.0f - pi[a] / old_p);
+    pol = fabsf(adv) * (pd < lo ? lo : pd);
+    const float dv = v - old_v;
+    const float vc = old_v + (dv < -ev ? -ev : (dv > ev ? ev : dv));
+    const float ea = vc - ret, eb = v - ret;
+    const float sa = ea * ea, sb = eb * eb;
+    val = (sa > sb || sa != sa) ? sa : sb;
+}
+
+// the workgroup's sum of Q quantities: a butterfly over the wavefront, then the waves in order; lane q < Q returns quantity q
+template <int Q>
+__device__ __forceinline__ double block_sums(const double (&x)[Q], double *wave_part) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int q = 0; q < Q; ++q) {
+        const double s = wave_sum(x[q]);
+        if (lane == 0) wave_part[wave * Q + q] = s;
+    }
+    __syncthreads();
+    double s = 0.0;
+    if (threadIdx.x < Q) {
+        s = wave_part[threadIdx.x];
+        for (int w = 1; w < PPO_WAVES; ++w) s += wave_part[w * Q + threadIdx.x];
+    }
+    return s;
+}
+
 __global__ __launch_bounds__(PPO_THREADS) void k_ppo_rows(sl_ppo_loss p, float *__restrict__ entropy_out,
                                                           double *__restrict__ partial) {
     extern __shared__ double lds[];
@@ -100,73 +143,112 @@ __global__ __launch_bounds__(PPO_THREADS) void k_ppo_rows(sl_ppo_loss p, float *
     if ((int)threadIdx.x < nrows) {
         long long r;
         int a;
-        if (ppo_row(p, i, r, a)) {
-            const float *pi = tile + threadIdx.x * S;
-            for (int k = 0; k < A; ++k) {
-                const float pk = pi[k];
-                const float t = (-pk) * logf(pk + 1e-12f);
-                ent = k ? ent + t : t;
-            }
-            const float adv = p.advantages[r], old_p = p.action_prob[r], old_v = p.old_values[r], ret = p.returns[r];
-            const float v = p.values[i];
-            const float lo = -(float)p.eps_policy, ev = (float)p.eps_value;
-            const float pd = sign_of(adv) * (1.0f - pi[a] / old_p);
-            pol = fabsf(adv) * (pd < lo ? lo : pd);
-            const float dv = v - old_v;
-            const float vc = old_v + (dv < -ev ? -ev : (dv > ev ? ev : dv));
-            const float ea = vc - ret, eb = v - ret;
-            const float sa = ea * ea, sb = eb * eb;
-            val = (sa > sb || sa != sa) ? sa : sb;
-        }
+        if (ppo_row(p, i, r, a)) ppo_row_terms(p, i, r, a, tile + threadIdx.x * S, pol, val, ent);
         entropy_out[i] = ent;
     }
-    const double s0 = wave_sum((double)pol), s1 = wave_sum((double)val), s2 = wave_sum((double)ent);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        wave_part[wave * 3 + 0] = s0;
-        wave_part[wave * 3 + 1] = s1;
-        wave_part[wave * 3 + 2] = s2;
-    }
+    const double x[3] = {(double)pol, (double)val, (double)ent};
+    const double s = block_sums<3>(x, wave_part);
+    if (threadIdx.x < 3) partial[(long long)blockIdx.x * 3 + threadIdx.x] = s;
+}
+
+// The report pass: rows [first_row, first_row + p.n) of a batch of p.N rows, p.values and p.policy being the model's outputs
+// for this chunk alone.  The same tile, the same per-row body and the same tree as k_ppo_rows, so a workgroup's first three
+// partials are the ones k_ppo_rows writes for the same 256 rows; two more carry the float64 sums of old_values and
+// advantages.  The workgroup's slot is its place in the WHOLE batch: however the batch is cut into chunks of a multiple of
+// 256 rows, the workspace ends up holding the same numbers.
+__global__ __launch_bounds__(PPO_THREADS) void k_ppo_report_rows(sl_ppo_loss p, long long first_row,
+                                                                 double *__restrict__ partial) {
+    extern __shared__ double lds[];
+    double *wave_part = lds;                                // [PPO_WAVES][SL_PPO_REPORT_PARTIALS]
+    float *tile = (float *)(lds + PPO_WAVES * SL_PPO_REPORT_PARTIALS);
+    const int A = p.n_actions, S = tile_stride(A);
+    const long long row0 = (long long)blockIdx.x * PPO_THREADS;
+    const int nrows = (int)(p.n - row0 < PPO_THREADS ? p.n - row0 : PPO_THREADS);
+    tile_load(p.policy, row0, nrows, A, tile);
     __syncthreads();
-    if (threadIdx.x < 3) {
-        double s = wave_part[threadIdx.x];
-        for (int w = 1; w < PPO_WAVES; ++w) s += wave_part[w * 3 + threadIdx.x];
-        partial[(long long)blockIdx.x * 3 + threadIdx.x] = s;
+
+    float pol = 0.f, val = 0.f, ent = 0.f, old_v = 0.f, adv = 0.f;
+    if ((int)threadIdx.x < nrows) {
+        const long long i = row0 + threadIdx.x, r = first_row + i;      // (the launcher checked first_row + p.n <= p.N)
+        const long long act = p.actions[r];
+        if (act < 0 || act >= A) {
+            atomicOr((unsigned long long *)p.status, (unsigned long long)SL_PPO_BAD_ACTION);
+        } else {
+            ppo_row_terms(p, i, r, (int)act, tile + threadIdx.x * S, pol, val, ent);
+            old_v = p.old_values[r];
+            adv = p.advantages[r];
+        }
     }
+    const double x[SL_PPO_REPORT_PARTIALS] = {(double)pol, (double)val, (double)ent, (double)old_v, (double)adv};
+    const double s = block_sums<SL_PPO_REPORT_PARTIALS>(x, wave_part);
+    if (threadIdx.x < SL_PPO_REPORT_PARTIALS)
+        partial[(first_row / PPO_THREADS + blockIdx.x) * SL_PPO_REPORT_PARTIALS + threadIdx.x] = s;
+}
+
+// Q partials per workgroup, added in index order by lane q < Q -> total[q]; the workgroup is FINISH_CHUNK lanes
+template <int Q>
+__device__ __forceinline__ void sum_partials(const double *__restrict__ partial, long long blocks, double *stage,
+                                             double *total) {
+    double s = 0.0;
+    for (long long b0 = 0; b0 < blocks; b0 += FINISH_CHUNK) {
+        const int nb = (int)(blocks - b0 < FINISH_CHUNK ? blocks - b0 : FINISH_CHUNK);
+        for (int j = threadIdx.x; j < nb * Q; j += FINISH_CHUNK) stage[j] = partial[b0 * Q + j];
+        __syncthreads();
+        if (threadIdx.x < Q)
+            for (int b = 0; b < nb; ++b) s += stage[b * Q + threadIdx.x];
+        __syncthreads();
+    }
+    if (threadIdx.x < Q) total[threadIdx.x] = s;
+    __syncthreads();
+}
+
+// the means over n rows, the entropy term, the total, the flag and n -> the first seven doubles of `out`; returns the total
+__device__ __forceinline__ double ppo_totals(const sl_ppo_loss &p, double n, const double *total, double *__restrict__ out) {
+    const double pm = total[0] / n, vm = total[1] / n, em = total[2] / n;
+    const double clip = (double)(float)p.entropy_clip;
+    const bool open = (float)em <= (float)p.entropy_clip;       // the comparison the reference makes in float32
+    const double term = -(double)(float)p.entropy_reg * (open ? em : clip);
+    const double loss = pm + (double)(float)p.vf_coef * vm + term;
+    out[SL_PPO_SUM_POLICY] = pm;
+    out[SL_PPO_SUM_VALUE] = vm;
+    out[SL_PPO_SUM_ENTROPY] = em;
+    out[SL_PPO_SUM_ENTROPY_TERM] = term;
+    out[SL_PPO_SUM_LOSS] = loss;
+    out[SL_PPO_SUM_FLAG] = open ? 1.0 : 0.0;
+    out[SL_PPO_SUM_N] = n;
+    return loss;
 }
 
 __global__ __launch_bounds__(FINISH_CHUNK) void k_ppo_finish(sl_ppo_loss p, const double *__restrict__ partial,
                                                             long long blocks, double *__restrict__ sums_out) {
     __shared__ double stage[FINISH_CHUNK * 3];
     __shared__ double total[3];
-    double s = 0.0;
-    for (long long b0 = 0; b0 < blocks; b0 += FINISH_CHUNK) {
-        const int nb = (int)(blocks - b0 < FINISH_CHUNK ? blocks - b0 : FINISH_CHUNK);
-        for (int j = threadIdx.x; j < nb * 3; j += FINISH_CHUNK) stage[j] = partial[b0 * 3 + j];
-        __syncthreads();
-        if (threadIdx.x < 3)
-            for (int b = 0; b < nb; ++b) s += stage[b * 3 + threadIdx.x];
-        __syncthreads();
-    }
-    if (threadIdx.x < 3) total[threadIdx.x] = s;
-    __syncthreads();
+    sum_partials<3>(partial, blocks, stage, total);
     if (threadIdx.x == 0) {
-        const double n = (double)p.n;
-        const double pm = total[0] / n, vm = total[1] / n, em = total[2] / n;
-        const double clip = (double)(float)p.entropy_clip;
-        const bool open = (float)em <= (float)p.entropy_clip;       // the comparison the reference makes in float32
-        const double term = -(double)(float)p.entropy_reg * (open ? em : clip);
-        const double loss = pm + (double)(float)p.vf_coef * vm + term;
-        sums_out[SL_PPO_SUM_POLICY] = pm;
-        sums_out[SL_PPO_SUM_VALUE] = vm;
-        sums_out[SL_PPO_SUM_ENTROPY] = em;
-        sums_out[SL_PPO_SUM_ENTROPY_TERM] = term;
-        sums_out[SL_PPO_SUM_LOSS] = loss;
-        sums_out[SL_PPO_SUM_FLAG] = open ? 1.0 : 0.0;
-        sums_out[SL_PPO_SUM_N] = n;
+        const double loss = ppo_totals(p, (double)p.n, total, sums_out);
         float *f = (float *)(sums_out + SL_PPO_SUM_LOSS_F32);     // the total as float32 in the slot's first four bytes
         f[0] = (float)loss;
         f[1] = 0.f;
+    }
+}
+
+// the report's finish: the divisor is the BATCH's row count
+__global__ __launch_bounds__(FINISH_CHUNK) void k_ppo_report_finish(sl_ppo_loss p, const double *__restrict__ partial,
+                                                                   long long blocks, double *__restrict__ out) {
+    __shared__ double stage[FINISH_CHUNK * SL_PPO_REPORT_PARTIALS];
+    __shared__ double total[SL_PPO_REPORT_PARTIALS];
+    sum_partials<SL_PPO_REPORT_PARTIALS>(partial, blocks, stage, total);
+    if (threadIdx.x == 0) {
+        const double n = (double)p.N;
+        const double loss = ppo_totals(p, n, total, out);
+        const double values = total[3] / n, advantages = total[4] / n;
+        out[SL_PPO_REPORT_VALUES] = values;
+        out[SL_PPO_REPORT_ADVANTAGES] = advantages;
+        float *f = (float *)(out + SL_PPO_REPORT_F32);            // what the reference logs, in the precision it logs it
+        f[SL_PPO_REPORT_F32_LOSS] = (float)loss;
+        f[SL_PPO_REPORT_F32_ENTROPY] = (float)(total[2] / n);
+        f[SL_PPO_REPORT_F32_VALUES] = (float)values;
+        f[SL_PPO_REPORT_F32_ADVANTAGES] = (float)advantages;
     }
 }
 
@@ -312,6 +394,20 @@ hipError_t launch_ppo_loss_forward(const sl_ppo_loss &p, float *entropy_out, dou
     if (err != hipSuccess) return err;
     hipLaunchKernelGGL(k_ppo_finish, dim3(1), dim3(FINISH_CHUNK), 0, stream, p, (const double *)workspace, (long long)blocks,
                        sums_out);
+    return hipGetLastError();
+}
+
+size_t ppo_report_workspace_bytes(long long N) { return (size_t)ppo_blocks(N) * SL_PPO_REPORT_PARTIALS * sizeof(double); }
+
+hipError_t launch_ppo_report_rows(const sl_ppo_loss &p, long long first_row, double *partial, hipStream_t stream) {
+    const size_t lds = PPO_WAVES * SL_PPO_REPORT_PARTIALS * sizeof(double) + tile_bytes(p.n_actions);
+    hipLaunchKernelGGL(k_ppo_report_rows, dim3(ppo_blocks(p.n)), dim3(PPO_THREADS), lds, stream, p, first_row, partial);
+    return hipGetLastError();
+}
+
+hipError_t launch_ppo_report_finish(const sl_ppo_loss &p, const double *partial, long long blocks, double *out,
+                                    hipStream_t stream) {
+    hipLaunchKernelGGL(k_ppo_report_finish, dim3(1), dim3(FINISH_CHUNK), 0, stream, p, partial, blocks, out);
     return hipGetLastError();
 }
 

@@ -5,7 +5,10 @@ The PPO update on the device: what the reference does with a training batch (tra
 entropy bonus with their gradients, fused into one pass forward (plus a one-workgroup finish) and one backward
 (``slhip_ppo_loss_forward`` / ``_backward``, sl_ppo.hip).  ``MinibatchDeal`` cuts an epoch's rows into the reference's
 minibatches, ``minibatch_obs`` fetches a minibatch's observations, widened to float32 in the same pass, and
-``train_batch`` is the loop of ``PPO.train_batch`` over these pieces.  Nothing here visits the host.
+``train_batch`` is the loop of ``PPO.train_batch`` over these pieces.  ``ppo_report`` is the report of ``PPO.train``
+(:199-205) over a batch too large for one model call, evaluated chunk by chunk with the same bits however it is cut
+(``slhip_ppo_report_rows`` / ``_finish``), and ``PPOTrainer.train`` the loop of ``PPO.train`` (:184-219): when to report,
+when to test.  Nothing here visits the host but ``check_status`` and ``ppo_report.scalars``.
 
 The reference's rule has four details a textbook PPO does not: the policy clamp is ONE-sided (``max(pd, -eps)`` on
 ``pd = sign(A) * (1 - pi / pi_old)``), the value term is the MAXIMUM of the clipped and the unclipped squared error, the
@@ -28,6 +31,20 @@ def _float_rows(x, torch, name, n=None):
     if n is not None and x.numel() != n:
         raise ValueError("ppo_loss: %s has %d elements, %d expected" % (name, x.numel(), n))
     return x if x.is_contiguous() else x.contiguous()
+
+
+def _batch_fields(batch, dev, torch, who):
+    """The five per-row scalars of a training batch, checked: flat, contiguous, on ``dev``, of one length."""
+    fixed = []
+    for name in _FIELDS:
+        x = getattr(batch, name)
+        want = torch.int64 if name == "actions" else torch.float32
+        if not (torch.is_tensor(x) and x.device == dev and x.dtype == want and x.dim() == 1):
+            raise ValueError("%s: batch.%s must be a flat %s tensor on the policy's device" % (who, name, want))
+        fixed.append(x if x.is_contiguous() else x.contiguous())
+    if any(x.numel() != fixed[0].numel() for x in fixed):
+        raise ValueError("%s: the batch's fields differ in length" % who)
+    return fixed
 
 
 def _loss_function():
@@ -113,17 +130,8 @@ def ppo_loss(values, policy, batch, rows=None, *, eps_policy=0.2, eps_value=0.2,
     policy = _float_rows(policy, torch, "policy")
     values = _float_rows(values, torch, "values", n).reshape(n)
     dev = policy.device
-    fixed = []
-    for name in _FIELDS:
-        x = getattr(batch, name)
-        want = torch.int64 if name == "actions" else torch.float32
-        if not (torch.is_tensor(x) and x.device == dev and x.dtype == want and x.dim() == 1):
-            raise ValueError("ppo_loss: batch.%s must be a flat %s tensor on the policy's device" % (name, want))
-        fixed.append(x if x.is_contiguous() else x.contiguous())
-    actions, action_prob, returns, advantages, old_values = fixed
+    actions, action_prob, returns, advantages, old_values = _batch_fields(batch, dev, torch, "ppo_loss")
     N = actions.numel()
-    if any(x.numel() != N for x in fixed):
-        raise ValueError("ppo_loss: the batch's fields differ in length")
     if rows is None:
         if n != N:
             raise ValueError("ppo_loss: without rows the model outputs must cover the whole batch (%d rows, not %d)" % (N, n))
@@ -286,3 +294,186 @@ def train_batch(model, optimizer, batch, deal, first_epoch, epochs_per_batch=3, 
             optimizer.step()
             sums = ppo_loss.sums
     return sums
+
+
+# -------------------------------------------------------------------------------------------------------------- the report
+
+def ppo_report(model, batch, *, chunk_rows=8192, eps_policy=0.2, eps_value=0.2, vf_coef=0.5, entropy_reg=0.01,
+               entropy_clip=1.0, status=None):
+    """
+    The report of ``PPO.train`` (training/ppo.py:199-205) -- ``calculate_loss`` on the WHOLE batch, its loss, the mean
+    entropy and the means of ``batch.values`` and ``batch.advantages`` -- without a host visit and without one model call on
+    the whole batch: under ``torch.no_grad()`` the model is called on ``chunk_rows`` rows of ``batch.obs`` at a time (a uint8
+    store is widened to float32, as ``minibatch_obs`` widens it) and every chunk's outputs go through
+    ``slhip_ppo_report_rows``; one ``slhip_ppo_report_finish`` follows.  The loss clips the entropy bonus at the batch's mean
+    entropy, so the chunks leave float64 partial sums per 256 rows, each at its place in the batch, and the finish adds them
+    in order: the result does not depend on ``chunk_rows``, bit for bit, and its first seven doubles are ``ppo_loss.sums``
+    of one ``ppo_loss(values, policy, batch)`` over the whole batch.
+
+    ``chunk_rows`` must be a positive multiple of 256 (ValueError).  -> the float64 device tensor ``[PPO_REPORT_DOUBLES]``:
+    ``_hip.PPO_SUMS``, the mean of ``batch.values``, the mean of ``batch.advantages``, and in the last two slots the four
+    scalars the reference logs as float32 (``_hip.PPO_REPORT_SCALARS``).  ``ppo_report.scalars(t)`` reads those four back.
+    A bad action raises ``PPO_BAD_ACTION`` in ``status`` (``ppo_loss.status`` when None) and its row adds nothing.
+    """
+    import torch
+    chunk_rows = int(chunk_rows)
+    if chunk_rows < 1 or chunk_rows % 256:
+        raise ValueError("ppo_report: chunk_rows must be a positive multiple of 256, not %d" % chunk_rows)
+    obs = batch.obs
+    if not (torch.is_tensor(obs) and obs.is_cuda):
+        raise ValueError("ppo_report: batch.obs must be a device tensor [N, ...]")
+    dev = obs.device
+    actions, action_prob, returns, advantages, old_values = _batch_fields(batch, dev, torch, "ppo_report")
+    N = actions.numel()
+    if N < 1 or obs.shape[0] != N:
+        raise ValueError("ppo_report: batch.obs has %d rows, the batch %d" % (obs.shape[0], N))
+    if status is None:
+        status = _status_word(dev)
+    lib = _hip.lib()
+    s = _hip.PpoLoss()
+    s.N = N
+    s.eps_policy, s.eps_value, s.vf_coef, s.entropy_reg, s.entropy_clip = (
+        float(eps_policy), float(eps_value), float(vf_coef), float(entropy_reg), float(entropy_clip))
+    for name, t in (("actions", actions), ("action_prob", action_prob), ("old_values", old_values), ("returns", returns),
+                    ("advantages", advantages), ("status", status)):
+        setattr(s, name, t.data_ptr())
+    work = torch.empty(lib.slhip_ppo_report_workspace_bytes(N) // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(_hip.PPO_REPORT_DOUBLES, dtype=torch.float64, device=dev)
+    stream = _hip.current_stream_ptr()
+    with torch.no_grad():
+        for lo in range(0, N, chunk_rows):
+            x = obs[lo:lo + chunk_rows]
+            values, policy = model(x.to(torch.float32) if x.dtype == torch.uint8 else x)
+            n = x.shape[0]
+            if policy.dim() != 2 or policy.shape[0] != n:
+                raise ValueError("ppo_report: the model must return a policy [n, n_actions] for n rows")
+            policy = _float_rows(policy, torch, "policy")
+            values = _float_rows(values, torch, "values", n)
+            s.n, s.n_actions, s.values, s.policy = n, policy.shape[1], values.data_ptr(), policy.data_ptr()
+            rc = lib.slhip_ppo_report_rows(C.byref(s), lo, _hip.ptr(work), stream)
+            if rc:
+                _hip.check(rc)
+    rc = lib.slhip_ppo_report_finish(C.byref(s), _hip.ptr(work), work.numel() // _hip.PPO_REPORT_PARTIALS, _hip.ptr(out),
+                                     stream)
+    if rc:
+        _hip.check(rc)
+    return out
+
+
+def _report_scalars(report):
+    """The four values the reference logs, read back from a ``ppo_report`` tensor (ONE host visit): a dict of Python
+    floats keyed ``loss``, ``entropy``, ``values``, ``advantages`` -- float32 numbers, the precision the reference logs."""
+    import torch
+    four = report[_hip.PPO_REPORT_F32:_hip.PPO_REPORT_F32 + 2].view(torch.float32).cpu().tolist()
+    return dict(zip(_hip.PPO_REPORT_SCALARS, four))
+
+
+ppo_report.scalars = _report_scalars
+
+
+# ------------------------------------------------------------------------------------------------------------- the trainer
+
+class PPOTrainer(object):
+    """
+    The loop of ``PPO.train`` (training/ppo.py:184-219) without checkpointing, over a ``VectorRunner`` or a
+    ``MultiAgentRunner``.
+
+    Per iteration: ``round_up(num_steps, interval)`` for the report and the test interval BEFORE the batch,
+    ``runner.gen_training_batch(steps_per_env, gamma, lmda)``, ``train_batch`` over epochs ``batches_done *
+    epochs_per_batch ...`` of the ``MinibatchDeal`` of the batch's row count (one deal per distinct row count: a
+    multi-agent window's varies; the epoch counter runs on across windows and ``train()`` calls), ``on_batch(num_steps)``
+    where the reference checkpoints, then the reference's two ``>=`` tests: ``on_report(num_steps, ppo_report(...))`` when
+    the report is due and ``on_report`` was given -- without it the model is not called, as the reference reports only with
+    a logger -- and ``test_runner.run_episodes()`` when a test is due and ``test_runner`` was given (which leaves
+    ``runner.num_steps`` alone: the test runner counts for itself).
+
+    ``events`` (with ``record_events``) holds ``(num_steps after the batch, reported, tested)`` per iteration.
+    ``host_visits`` counts the ``.item()`` calls made: none over a single-agent runner, one per window over a multi-agent
+    runner (the row count its ``gen_training_batch`` reads).  ``loss_kwargs`` are ``ppo_loss``'s hyper-parameters, for the
+    update and the report alike.
+    """
+
+    def __init__(self, runner, model, optimizer, *, steps_per_env=20, num_minibatches=4, epochs_per_batch=3, gamma=0.97,
+                 lmda=0.95, report_interval=960, test_interval=500000, seed=0, test_runner=None, on_report=None,
+                 on_batch=None, report_chunk_rows=8192, record_events=False, **loss_kwargs):
+        for name, v in (("steps_per_env", steps_per_env), ("num_minibatches", num_minibatches),
+                        ("epochs_per_batch", epochs_per_batch), ("report_interval", report_interval),
+                        ("test_interval", test_interval)):
+            if int(v) < 1:
+                raise ValueError("PPOTrainer: %s must be at least 1" % name)
+        if int(report_chunk_rows) < 1 or int(report_chunk_rows) % 256:
+            raise ValueError("PPOTrainer: report_chunk_rows must be a positive multiple of 256")
+        unknown = set(loss_kwargs) - {"eps_policy", "eps_value", "vf_coef", "entropy_reg", "entropy_clip"}
+        if unknown:
+            raise TypeError("PPOTrainer: unknown arguments %s" % sorted(unknown))
+        self.runner, self.model, self.optimizer = runner, model, optimizer
+        self.steps_per_env, self.num_minibatches = int(steps_per_env), int(num_minibatches)
+        self.epochs_per_batch, self.gamma, self.lmda = int(epochs_per_batch), float(gamma), float(lmda)
+        self.report_interval, self.test_interval = int(report_interval), int(test_interval)
+        self.seed, self.test_runner, self.on_report, self.on_batch = int(seed), test_runner, on_report, on_batch
+        self.report_chunk_rows, self.record_events, self.loss_kwargs = int(report_chunk_rows), bool(record_events), loss_kwargs
+        self.events = []
+        self.batches_done = 0           # the deal's epoch is batches_done * epochs_per_batch + k
+        self.host_visits = 0            # .item() calls made by train(): the row count of a multi-agent window
+        self.sums = None                # ppo_loss.sums of the last minibatch
+        self._deals = {}
+
+    @property
+    def num_steps(self):
+        return self.runner.num_steps
+
+    def deal(self, num_rows):
+        """The ``MinibatchDeal`` of batches of ``num_rows`` rows, made on first use."""
+        deal = self._deals.get(num_rows)
+        if deal is None:
+            deal = self._deals[num_rows] = MinibatchDeal(num_rows, self.num_minibatches, self.seed)
+        return deal
+
+    def train_batch(self, batch):
+        """``train_batch`` on the next ``epochs_per_batch`` epochs of the batch's deal."""
+        return train_batch(self.model, self.optimizer, batch, self.deal(int(batch.actions.shape[0])),
+                           self.batches_done * self.epochs_per_batch, self.epochs_per_batch, **self.loss_kwargs)
+
+    def report(self, batch):
+        """``ppo_report`` of the batch -> the device tensor."""
+        return ppo_report(self.model, batch, chunk_rows=self.report_chunk_rows, **self.loss_kwargs)
+
+    def test(self):
+        return self.test_runner.run_episodes()
+
+    def train(self, steps):
+        """``PPO.train(steps)``: iterations until ``num_steps`` has grown by at least ``steps``."""
+        from .dqn import round_up
+        runner = self.runner
+        multi = bool(getattr(runner, "_multi_agent", False))
+        max_steps = runner.num_steps + int(steps)
+        while runner.num_steps < max_steps:
+            next_report = round_up(runner.num_steps, self.report_interval)
+            next_test = round_up(runner.num_steps, self.test_interval)
+            batch = runner.gen_training_batch(self.steps_per_env, self.gamma, self.lmda)
+            if multi:
+                self.host_visits += 1
+            self.sums = self.train_batch(batch)
+            self.batches_done += 1
+            num_steps = runner.num_steps
+            if self.on_batch is not None:
+                self.on_batch(num_steps)
+            reported = num_steps >= next_report and self.on_report is not None
+            if reported:
+                self.on_report(num_steps, self.report(batch))
+            tested = self.test_runner is not None and num_steps >= next_test
+            if tested:
+                self.test()
+            if self.record_events:
+                self.events.append((num_steps, reported, tested))
+
+    def state_dict(self):
+        """What a checkpoint needs beside the model's and the optimiser's own: where the schedule and the deal stand."""
+        return dict(num_steps=int(self.runner.num_steps), batches_done=int(self.batches_done), seed=int(self.seed))
+
+    def load_state_dict(self, state):
+        self.runner.num_steps = int(state["num_steps"])
+        self.batches_done = int(state["batches_done"])
+        if int(state["seed"]) != self.seed:
+            self.seed = int(state["seed"])
+            self._deals = {}

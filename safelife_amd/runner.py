@@ -209,11 +209,19 @@ class VectorRunner(_Runner):
     copy_obs : bool              ``obs`` / ``next_obs`` of a result are views of the env's tensor, which the next
                                  step overwrites; True returns an own copy of ``obs`` (what a replay buffer needs)
     cast_obs : bool              True: the policy gets float32 (training/ppo.py:64); False: the env's tensor as it is
+    seed : int or None           an int: the draw is the library's kernel (``slhip_sample_actions``), the action of env e
+                                 at step c a function of ``(seed, c, env.env_offset + e)`` and its probabilities alone --
+                                 the rule of the other runners; ``generator`` is then not used.  None: ``torch.multinomial``
     """
 
-    def __init__(self, env, policy, generator=None, copy_obs=True, cast_obs=True):
+    _bad_output = "policy must return probabilities [num_envs, n_actions]"
+
+    def __init__(self, env, policy, generator=None, copy_obs=True, cast_obs=True, seed=None):
         super(VectorRunner, self).__init__(env, cast_obs)
         self.policy, self.generator, self.copy_obs = policy, generator, copy_obs
+        self.seed = None
+        if seed is not None:
+            self._device_draws(seed)
         # env.num_resets of the reference
         self.num_resets = self.torch.zeros(env.num_envs, device=env.device, dtype=self.torch.int64)
 
@@ -240,10 +248,15 @@ class VectorRunner(_Runner):
         the fused step."""
         obs, agent_ids = self.obs_for_envs()
         values, policies = self._call(self.policy, obs)
-        actions = self.torch.multinomial(policies, 1, generator=self.generator).squeeze(1)
-        self._mask_retired(actions)
+        if self.seed is None:
+            stepped = actions = self._mask_retired(self.torch.multinomial(policies, 1, generator=self.generator).squeeze(1))
+        else:
+            probs = self._draw_input(policies)
+            self._draw(self._lib.slhip_sample_actions, _hip.ptr(probs), self._rows, probs.shape[1])
+            stepped = self._mask_retired(self.actions)          # the int32 tensor the step kernel reads
+            actions = stepped.to(self.torch.int64)              # an own copy, int64 as the multinomial's
         kept = obs.clone() if self.copy_obs else obs
-        next_obs, rewards, done = self.act_on_envs(actions)
+        next_obs, rewards, done = self.act_on_envs(stepped)
         return StepResult(kept, actions, rewards, done, next_obs, agent_ids, policies, values)
 
     def run_steps(self, n):
