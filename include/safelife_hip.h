@@ -1680,6 +1680,46 @@ int slhip_dqn_loss_forward(const sl_dqn_loss *loss, float *td_out, double *sums_
 int slhip_dqn_loss_backward(const sl_dqn_loss *loss, const float *grad_loss, const float *grad_td, const float *td,
                             float *d_q, void *stream);
 
+/* ---- the state digest: a 64-bit checksum of device memory, per segment of a table (additive again: three symbols and one
+ * struct, nothing existing changes; SL_ABI_VERSION stays where it is) ---------------------------------------------------------
+ * What a checkpoint uses to tell that what it uploaded is what it saved, and what two runs use to compare their whole state,
+ * without a host copy.  An INTEGRITY checksum, NOT a cryptographic hash: it is not hard to find two inputs that collide.
+ *
+ * All arithmetic mod 2^64.  mix(z) is splitmix64's finaliser:
+ *   z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31
+ * and G = 0x9E3779B97F4A7C15.  A segment of n bytes is read as ceil(n / 8) little-endian 64-bit words w_i (i from 0), bytes
+ * past n counting as zero:
+ *   acc    = sum over i of mix(w_i + mix(salt) + (i + 1) * G)
+ *   digest = mix(acc + mix((salt ^ n) + G))
+ * Known answers: no bytes, salt 0 -> 0x48218226ff3cd4bf; the bytes 0..19, salt 0 -> 0x0c817c4bd668decf; the same with salt 7 ->
+ * 0x510af6e63ac50e25.  The sum is an integer sum, so it does not depend on the order of its terms: the split over workgroups is
+ * free, and two calls over the same bytes are bit-equal by construction.
+ *
+ * `segments` and `out` are DEVICE arrays of n_segments entries (8-byte aligned); out[s] is the digest of segment s, and nothing
+ * beyond out[n_segments - 1] is written.  A segment's ptr may have ANY byte alignment and its bytes may be 0 (ptr is then not
+ * looked at).  The kernels only read the segments, and never a byte outside [ptr, ptr + bytes): words whose aligned 8-byte
+ * carriers lie wholly inside the segment are read with aligned loads, 16 bytes per lane; the first and last few are put together
+ * byte by byte.
+ *
+ * `workspace` is a device buffer of slhip_state_digest_workspace_bytes(bytes, n_segments) bytes, 8-byte aligned.  Its HEAD is
+ * the chunk prefix table, n_segments + 1 words, which the CALLER fills before the call with what
+ * slhip_state_digest_prefix(bytes, n_segments, ...) computes on the host from the same byte counts (it rides along with the
+ * upload of the segment table); the rest is the kernels' scratch.  The table deals fixed-size chunks of ALL segments over one
+ * capped grid, so a table of many 4-byte counters and one ring of hundreds of MB keeps every workgroup busy.
+ * Two launches: the chunk pass and a one-wavefront-per-segment finish.  No atomics, no floating point. */
+typedef struct sl_digest_segment {  /* 16 bytes */
+    const void *ptr;                /* device memory, any alignment */
+    unsigned long long bytes;
+} sl_digest_segment;
+
+size_t slhip_state_digest_workspace_bytes(const unsigned long long *bytes /* host */, int n_segments);
+
+/* prefix_out: HOST, n_segments + 1 words -- the head of the workspace (see above) */
+int slhip_state_digest_prefix(const unsigned long long *bytes /* host */, int n_segments, unsigned long long *prefix_out);
+
+int slhip_state_digest(const sl_digest_segment *segments /* device */, int n_segments, unsigned long long salt,
+                       unsigned long long *out /* device, n_segments */, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

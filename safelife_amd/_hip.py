@@ -47,6 +47,7 @@ EXPORTS = (
     "slhip_minibatch_keys",
     "slhip_ppo_report_workspace_bytes", "slhip_ppo_report_rows", "slhip_ppo_report_finish",
     "slhip_dqn_workspace_bytes", "slhip_dqn_loss_forward", "slhip_dqn_loss_backward",
+    "slhip_state_digest_workspace_bytes", "slhip_state_digest_prefix", "slhip_state_digest",
 )
 PPO_BAD_ACTION, PPO_BAD_INDEX = 1, 2
 #: sums_out of slhip_ppo_loss_forward: the doubles' names in order; slot PPO_SUM_LOSS_F32 holds a float32, not a double
@@ -272,6 +273,11 @@ class DqnLoss(C.Structure):
                 + [(n, C.c_void_p) for n in ("q_values", "next_q_values", "action", "reward", "done", "index", "status")])
 
 
+class DigestSegment(C.Structure):
+    """struct sl_digest_segment (16 bytes)"""
+    _fields_ = [("ptr", C.c_void_p), ("bytes", C.c_ulonglong)]
+
+
 class EpisodeRun(C.Structure):
     """struct sl_episode_run (80 bytes)"""
     _fields_ = ([(n, C.c_int32) for n in ("B", "G", "env_offset", "N", "L", "n_agents")]
@@ -440,6 +446,10 @@ def lib():
         L.slhip_dqn_workspace_bytes.restype = C.c_size_t
         L.slhip_dqn_loss_forward.argtypes = [C.POINTER(DqnLoss), _p, _p, _p, _p]
         L.slhip_dqn_loss_backward.argtypes = [C.POINTER(DqnLoss), _p, _p, _p, _p, _p]
+        L.slhip_state_digest_workspace_bytes.argtypes = [_p, C.c_int]
+        L.slhip_state_digest_workspace_bytes.restype = C.c_size_t
+        L.slhip_state_digest_prefix.argtypes = [_p, C.c_int, _p]
+        L.slhip_state_digest.argtypes = [_p, C.c_int, C.c_ulonglong, _p, _p, _p]
         L.slhip_obs_to_policy.argtypes = [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]
         L.slhip_gather_unique_id.argtypes = [_p]
         L.slhip_gather_init.argtypes = [_p, C.c_int, C.c_int, C.POINTER(_p)]

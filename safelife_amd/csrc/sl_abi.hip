@@ -2279,4 +2279,25 @@ int slhip_dqn_loss_backward(const sl_dqn_loss *loss, const float *grad_loss, con
     return err == hipSuccess ? SL_OK : hip_fail(err, "dqn_loss_backward launch");
 }
 
+size_t slhip_state_digest_workspace_bytes(const unsigned long long *bytes, int n_segments) {
+    return (!bytes || n_segments < 1) ? 0 : sl::digest_workspace_bytes(bytes, n_segments);
+}
+
+int slhip_state_digest_prefix(const unsigned long long *bytes, int n_segments, unsigned long long *prefix_out) {
+    if (n_segments < 0 || !prefix_out || (n_segments && !bytes)) return fail(SL_E_ARG, "state_digest_prefix: bad arguments");
+    sl::digest_prefix(bytes, n_segments, prefix_out);
+    return SL_OK;
+}
+
+int slhip_state_digest(const sl_digest_segment *segments, int n_segments, unsigned long long salt, unsigned long long *out,
+                       void *workspace, void *stream) {
+    if (n_segments < 0) return fail(SL_E_ARG, "state_digest: n_segments < 0");
+    if (n_segments == 0) return SL_OK;
+    if (!segments || !out || !workspace) return fail(SL_E_ARG, "state_digest: null pointer");
+    if (((uintptr_t)segments | (uintptr_t)out | (uintptr_t)workspace) & 7)
+        return fail(SL_E_ARG, "state_digest: segments / out / workspace not 8-byte aligned");
+    const hipError_t err = sl::launch_state_digest(segments, n_segments, salt, out, workspace, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "state_digest launch");
+}
+
 }  // extern "C"

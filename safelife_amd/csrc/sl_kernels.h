@@ -180,6 +180,11 @@ size_t dqn_workspace_bytes(long long n);
 hipError_t launch_dqn_loss_forward(const sl_dqn_loss &p, float *td_out, double *sums_out, void *workspace, hipStream_t stream);
 hipError_t launch_dqn_loss_backward(const sl_dqn_loss &p, const float *grad_loss, const float *grad_td, const float *td,
                                     float *d_q, hipStream_t stream);
+// the state digest (sl_digest.hip): a 64-bit integrity checksum per segment of a table of device memory segments
+size_t digest_workspace_bytes(const unsigned long long *bytes, int n_segments);
+void digest_prefix(const unsigned long long *bytes, int n_segments, unsigned long long *prefix_out);
+hipError_t launch_state_digest(const sl_digest_segment *segments, int n_segments, unsigned long long salt,
+                               unsigned long long *out, void *workspace, hipStream_t stream);
 // envs [e_first, e_first + e_count) of the batch; actions / reward_t / done_t are indexed [t * tstride + e]
 // with the env's index in the whole batch
 // (sl_aql.hip dispatches the same kernel from queues of the library's own: PreparedStep below)

@@ -248,8 +248,8 @@ def round_up(x, r):
 
 class DQNTrainer(object):
     """
-    The loop of ``DQN.train`` (training/dqn.py:177-208) without checkpointing and testing, over a ``DQNRunner`` or a
-    ``MultiAgentDQNRunner`` and its replay buffer.
+    The loop of ``DQN.train`` (training/dqn.py:177-214) over a ``DQNRunner`` or a ``MultiAgentDQNRunner`` and its replay
+    buffer.
 
     Per iteration: ``round_up(num_steps, interval)`` for the three intervals BEFORE the step, epsilon from the schedule at
     that ``num_steps``, one ``runner.collect(1, epsilon, replay)`` (which adds ``env.num_envs`` to ``runner.num_steps``),
@@ -266,16 +266,37 @@ class DQNTrainer(object):
     0.03 from 4e6 on, to the last bit what the reference's ``epsilon_schedule`` returns).  ``on_report(num_steps, epsilon,
     sums)`` gets the device tensor of the optimise that carried the report flag.  ``record_events``: keep, per iteration,
     ``(num_steps after the step, epsilon, optimized, reported, target_updated)`` in ``events``.
+
+    ``checkpointer``: a ``checkpoint.Checkpointer`` (None: nothing is saved and nothing is computed).  Whether a save is
+    due is asked past the replay gate only, behind the target update, where the reference calls
+    ``save_checkpoint_if_needed`` (training/dqn.py:208), so the files carry the reference's steps; the file itself is
+    written at the END of that iteration, behind the test run and the event, with the loop's report flag, so that it is a
+    whole iteration: a ``train()`` call on a trainer loaded from it goes on where the interrupted call stood and owes
+    nothing (the reference's file, taken in front of ``run_episodes``, loses the test that was due, and its resumed
+    ``train()`` raises the report flag anew).  ``train()`` ends with a save (:214), behind which the next call starts as
+    the reference's does.  A checkpointer without a
+    ``root`` gets this trainer, both models (``training_model``, ``target_model``) and the optimiser.
+
+    ``test_runner``: a second ``DQNRunner`` / ``MultiAgentDQNRunner`` over an env with an ``EpisodeRun`` (None: no tests).
+    ``next_test = round_up(num_steps, test_interval)`` is taken with the other three intervals; past the replay gate and
+    behind the checkpoint, when ``num_steps >= next_test``, ``self.epsilon`` becomes ``epsilon_testing`` and
+    ``test_runner.run_episodes(epsilon=epsilon_testing)`` runs (training/dqn.py:210-212).  ``self.epsilon`` stays there
+    until the next iteration sets it, as in the reference; ``runner.num_steps`` is untouched; the tuples in ``events`` do
+    not change; the steps at which a test ran go to ``tests_run``.
     """
+
+    _checkpoint_children = ("runner", "replay", "test_runner")
 
     def __init__(self, runner, replay, training_model, target_model, optimizer, *, training_batch_size=96,
                  optimize_interval=32, target_update_interval=10000, report_interval=256, replay_initial=40000,
-                 epsilon_schedule=None, on_report=None, record_events=False):
+                 epsilon_schedule=None, on_report=None, record_events=False, checkpointer=None, test_runner=None,
+                 test_interval=100000, epsilon_testing=0.01):
         if epsilon_schedule is None:
             from .schedule import LinearSchedule
             epsilon_schedule = LinearSchedule(EPSILON_KNOTS, EPSILON_COEFFICIENTS)
         for name, v in (("training_batch_size", training_batch_size), ("optimize_interval", optimize_interval),
-                        ("target_update_interval", target_update_interval), ("report_interval", report_interval)):
+                        ("target_update_interval", target_update_interval), ("report_interval", report_interval),
+                        ("test_interval", test_interval)):
             if int(v) < 1:
                 raise ValueError("DQNTrainer: %s must be at least 1" % name)
         self.runner, self.replay = runner, replay
@@ -290,6 +311,14 @@ class DQNTrainer(object):
         self.sums = None                # dqn_loss.sums of the last optimise
         self.host_visits = 0            # exact len(replay) reads: .item() calls made by train()
         self._gate_open = False
+        self._needs_report, self._in_train = True, False    # the loop's report flag, as a checkpoint inside train() finds it
+        self.test_runner, self.test_interval = test_runner, int(test_interval)
+        self.epsilon_testing = float(epsilon_testing)
+        self.tests_run = []             # num_steps at which test episodes ran
+        self.checkpointer = checkpointer
+        if checkpointer is not None and checkpointer.root is None:
+            checkpointer.root, checkpointer.optimizer = self, optimizer
+            checkpointer.model = {"training_model": training_model, "target_model": target_model}
 
     @property
     def num_steps(self):
@@ -312,17 +341,20 @@ class DQNTrainer(object):
     def train(self, steps):
         """``DQN.train(steps)``: iterations until ``num_steps`` has grown by at least ``steps``."""
         runner = self.runner
-        needs_report = True
+        # (a trainer loaded from a file that was written inside a train() call goes on with that call's report flag)
+        needs_report = self._needs_report if self._in_train else True
+        self._in_train = False
         max_steps = runner.num_steps + int(steps)
         while runner.num_steps < max_steps:
             before = runner.num_steps
             next_opt = round_up(before, self.optimize_interval)
             next_update = round_up(before, self.target_update_interval)
             next_report = round_up(before, self.report_interval)
+            next_test = round_up(before, self.test_interval)
             self.epsilon = epsilon = float(self.epsilon_schedule(before))
             runner.collect(1, epsilon, self.replay)
             num_steps = runner.num_steps
-            optimized = reported = updated = False
+            optimized = reported = updated = save_due = False
             if self._replay_ready():
                 if num_steps >= next_report:
                     needs_report = True
@@ -335,5 +367,35 @@ class DQNTrainer(object):
                 if num_steps >= next_update:
                     updated = True
                     self.update_target()
+                save_due = self.checkpointer is not None and self.checkpointer.due(num_steps)
+                if self.test_runner is not None and num_steps >= next_test:
+                    self.epsilon = self.epsilon_testing
+                    self.test()
+                    self.tests_run.append(num_steps)
             if self.record_events:
                 self.events.append((num_steps, epsilon, optimized, reported, updated))
+            if save_due:
+                self._needs_report, self._in_train = needs_report, True
+                self.checkpointer.save(num_steps)
+        self._needs_report, self._in_train = needs_report, False
+        if self.checkpointer is not None:
+            self.checkpointer.save(runner.num_steps)
+
+    def test(self):
+        """``run_episodes`` of the test runner at ``epsilon_testing`` (training/dqn.py:211-212)."""
+        return self.test_runner.run_episodes(epsilon=self.epsilon_testing)
+
+    def _checkpoint_state(self):
+        """``checkpoint.py``: whether the replay gate has opened, and the events so far; the runner, the replay buffer and
+        the test runner carry the rest."""
+        config = dict(training_batch_size=self.training_batch_size, optimize_interval=self.optimize_interval,
+                      target_update_interval=self.target_update_interval, report_interval=self.report_interval,
+                      replay_initial=self.replay_initial, test_interval=self.test_interval,
+                      epsilon_testing=self.epsilon_testing)
+        scalars = dict(_gate_open=self._gate_open, _needs_report=self._needs_report, _in_train=self._in_train,
+                       host_visits=self.host_visits, epsilon=self.epsilon,
+                       events=self.events, tests_run=self.tests_run)
+        return config, scalars, {}
+
+    def _checkpoint_loaded(self):
+        self.events = [tuple(e) for e in self.events]

@@ -161,6 +161,14 @@ class _EpisodeHistoryBase(object):
         if rc:
             _hip.check(rc)
 
+    def _checkpoint_state(self):
+        """``checkpoint.py``: the slots with their frames, the listing, and where every watched env's episode stands."""
+        self._need_state()
+        config = dict(num_envs=self.num_envs, slots=self.slots, interval=self.interval, watch=self.watch.tolist(),
+                      time_limit=self.time_limit, board_shape=self.pool.shape)
+        names = ("owner", "cur_level", "cur_episode", "slot_state", "entries", "counters", "goals", "frames", "orders")
+        return config, {}, {k: self.t[k] for k in names}
+
     def _queue_replaced(self):
         """``side_effects_flush()`` has installed a fresh queue: the cursor starts over."""
         self.t["counters"][4].zero_()

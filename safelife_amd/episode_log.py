@@ -145,6 +145,15 @@ class _EpisodeLogBase(object):
         else:
             t["last_row"].masked_fill_(mask != 0, -1)
 
+    def _checkpoint_state(self):
+        """``checkpoint.py``: the row ring, the counters with the summaries' counts, values and Polyak weights (one buffer),
+        and what the log knows of every env's running episode."""
+        self._device_state()
+        config = dict(num_envs=self.num_envs, capacity=self.capacity, episode_type=self.episode_type,
+                      summary_polyak=self.summary_polyak, n_keys=self.n_keys, row_bytes=self.row_dtype.itemsize,
+                      side_effect_weights=self.side_effect_weights)
+        return config, {}, {k: self.t[k] for k in ("rows", "state", "cur_slot", "cur_required", "cur_episode", "last_row")}
+
     def join(self, count, records, scores, keys, n_cells):
         """The join of one flushed queue (device tensors: count int32 [1], records int32 [C,8], scores float64 [C,K,2], keys
         [C,K] 16-bit, n_cells int32 [C,K]; one entry per env episode) on the current stream."""

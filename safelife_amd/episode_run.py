@@ -196,6 +196,16 @@ class EpisodeRun(object):
         if rc:
             _hip.check(rc)
 
+    def _checkpoint_state(self):
+        """``checkpoint.py``: the result table and the counters of the last run.  A live run is refused."""
+        from . import checkpoint
+        checkpoint.refuse_run(self)
+        self._need_state()
+        config = dict(num_envs=self.num_envs, num_episodes=self.num_episodes, n_agents=self.n_agents,
+                      env_offset=self.env_offset, global_envs=self.global_envs, n_slots=self.n_slots)
+        names = ("active", "played", "base_episode", "counters", "results", "agent_results", "side_effects")
+        return config, dict(steps=self.steps, _live=self._live), {k: self.t[k] for k in names}
+
     def tickets(self, batch, weights=None, _scores=False):
         """The tickets of a ``SideEffectBatch``'s entries, int32 [capacity] on the device: -1 for a retired env's phantom
         episode, for an episode from before the run and for the slots past the batch's count."""

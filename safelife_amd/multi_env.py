@@ -270,6 +270,22 @@ class SafeLifeMultiAgentVectorEnv(object):
     def side_effects_join(self):
         self.base.side_effects_join()
 
+    # (the base env last: what both name -- schedule, log, run, history -- is then filed under this env)
+    _checkpoint_children = ("level_schedule", "episode_log", "episode_run", "episode_history", "base")
+
+    def _checkpoint_state(self):
+        """``checkpoint.py``: the agents' records, the per-agent level records (a schedule rewrites their required points),
+        the step's output and what the wrappers and the policy layout keep; boards, generators and the queue are the base
+        env's."""
+        config = dict(num_envs=self.num_envs, n_agents=self.n_agents, time_limit=self.time_limit,
+                      view_shape=self.view_shape, output_channels=self.output_channels)
+        tensors = {k: v for k, v in self.t.items() if k != "move_table"}
+        if self.obs is not None:
+            tensors["obs"] = self.obs
+        if self.policy_tensor is not None:
+            tensors["policy_tensor"] = self.policy_tensor
+        return config, {}, tensors
+
     def numpy(self, name):
         """Host copy of a state array: the single-agent env's names for what the env owns (board, goals, rng, num_steps,
         level_idx, episode_idx, goals_static, exit_locs), and per agent [B, A(, 2)]: agent_locs, old_value,

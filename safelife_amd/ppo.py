@@ -375,8 +375,7 @@ ppo_report.scalars = _report_scalars
 
 class PPOTrainer(object):
     """
-    The loop of ``PPO.train`` (training/ppo.py:184-219) without checkpointing, over a ``VectorRunner`` or a
-    ``MultiAgentRunner``.
+    The loop of ``PPO.train`` (training/ppo.py:184-219) over a ``VectorRunner`` or a ``MultiAgentRunner``.
 
     Per iteration: ``round_up(num_steps, interval)`` for the report and the test interval BEFORE the batch,
     ``runner.gen_training_batch(steps_per_env, gamma, lmda)``, ``train_batch`` over epochs ``batches_done *
@@ -391,11 +390,20 @@ class PPOTrainer(object):
     ``host_visits`` counts the ``.item()`` calls made: none over a single-agent runner, one per window over a multi-agent
     runner (the row count its ``gen_training_batch`` reads).  ``loss_kwargs`` are ``ppo_loss``'s hyper-parameters, for the
     update and the report alike.
+
+    ``checkpointer``: a ``checkpoint.Checkpointer`` (None: nothing is saved and nothing is computed).  Whether a save is
+    due is asked right behind ``on_batch``, where the reference calls ``save_checkpoint_if_needed`` (training/ppo.py:194), so
+    the files carry the reference's steps; the file itself is written at the END of that iteration, behind the report, the
+    test run and the event, so that it is a whole iteration: a run resumed from it owes nothing (the reference's file, taken
+    in front of ``run_episodes``, loses the test that was due).  ``train()`` ends with a save (:219).  A checkpointer without
+    a ``root`` gets this trainer, its model and its optimiser.
     """
+
+    _checkpoint_children = ("runner", "test_runner")
 
     def __init__(self, runner, model, optimizer, *, steps_per_env=20, num_minibatches=4, epochs_per_batch=3, gamma=0.97,
                  lmda=0.95, report_interval=960, test_interval=500000, seed=0, test_runner=None, on_report=None,
-                 on_batch=None, report_chunk_rows=8192, record_events=False, **loss_kwargs):
+                 on_batch=None, report_chunk_rows=8192, record_events=False, checkpointer=None, **loss_kwargs):
         for name, v in (("steps_per_env", steps_per_env), ("num_minibatches", num_minibatches),
                         ("epochs_per_batch", epochs_per_batch), ("report_interval", report_interval),
                         ("test_interval", test_interval)):
@@ -417,6 +425,9 @@ class PPOTrainer(object):
         self.host_visits = 0            # .item() calls made by train(): the row count of a multi-agent window
         self.sums = None                # ppo_loss.sums of the last minibatch
         self._deals = {}
+        self.checkpointer = checkpointer
+        if checkpointer is not None and checkpointer.root is None:
+            checkpointer.root, checkpointer.model, checkpointer.optimizer = self, model, optimizer
 
     @property
     def num_steps(self):
@@ -458,6 +469,7 @@ class PPOTrainer(object):
             num_steps = runner.num_steps
             if self.on_batch is not None:
                 self.on_batch(num_steps)
+            save_due = self.checkpointer is not None and self.checkpointer.due(num_steps)
             reported = num_steps >= next_report and self.on_report is not None
             if reported:
                 self.on_report(num_steps, self.report(batch))
@@ -466,6 +478,22 @@ class PPOTrainer(object):
                 self.test()
             if self.record_events:
                 self.events.append((num_steps, reported, tested))
+            if save_due:
+                self.checkpointer.save(num_steps)
+        if self.checkpointer is not None:
+            self.checkpointer.save(runner.num_steps)
+
+    def _checkpoint_state(self):
+        """``checkpoint.py``: where the deal stands, and the events so far; the runner and the test runner carry the
+        rest."""
+        config = dict(steps_per_env=self.steps_per_env, num_minibatches=self.num_minibatches,
+                      epochs_per_batch=self.epochs_per_batch, gamma=self.gamma, lmda=self.lmda,
+                      report_interval=self.report_interval, test_interval=self.test_interval, seed=self.seed,
+                      loss_kwargs=self.loss_kwargs)
+        return config, dict(batches_done=self.batches_done, host_visits=self.host_visits, events=self.events), {}
+
+    def _checkpoint_loaded(self):
+        self.events = [tuple(e) for e in self.events]
 
     def state_dict(self):
         """What a checkpoint needs beside the model's and the optimiser's own: where the schedule and the deal stand."""

@@ -133,6 +133,23 @@ class _Runner(object):
         self.env.step(actions)
         return self._reward().clone(), self.env.done.to(self.torch.bool)
 
+    _checkpoint_children = ("env",)
+
+    def _checkpoint_state(self):
+        """``checkpoint.py``: the step and draw counters, the action tensor the step kernel reads, the reset counters --
+        and, through the env, the observation the next model call gets."""
+        from . import checkpoint
+        checkpoint.refuse_runner(self)
+        config = dict(rows=self._rows, per_agent=self._per_agent, seed=self.seed, cast_obs=bool(self.cast_obs))
+        scalars = dict(num_steps=self.num_steps, _started=self._started, draws=self.draws)
+        tensors = dict(actions=self.actions)
+        if self._multi_agent:
+            buf = self._state.buffer
+            tensors.update(num_agent_steps=self.num_agent_steps, active=buf.active_now, num_resets=buf.num_resets)
+        else:
+            tensors.update(num_resets=self.num_resets)
+        return config, scalars, tensors
+
     def _live_run(self):
         """The env's ``EpisodeRun`` while a run is on (started), else None."""
         run = getattr(self.env, "episode_run", None)
@@ -376,6 +393,10 @@ class PipelinedRunner(object):
             # (the kernel's env e of this group is env offset + lo + e of the whole run: see slhip_sample_actions)
             self._groups.append((g, lo, hi, st, torch.cuda.stream(st), env.policy_tensor[lo:hi],
                                  self.actions.data_ptr() + 4 * lo, st.cuda_stream, _shifted_seed(self.seed, offset + lo)))
+
+    def _checkpoint_state(self):
+        from . import checkpoint
+        checkpoint.refuse_runner(self)
 
     def start(self):
         if not self._started:

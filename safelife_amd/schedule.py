@@ -370,6 +370,18 @@ class LevelSchedule(object):
         if rc:
             _hip.check(rc)
 
+    _CHECKPOINT_TENSORS = ("cur_slot", "ring", "count", "episodes", "pos", "best", "mean", "status", "probs", "pool_next")
+
+    def _checkpoint_state(self):
+        """``checkpoint.py``: the rings, the successor table of the last draw, and the host's counters (``_fraction_sent``:
+        the required points in the env's ``pool_scalars`` / ``pool_agents`` are the env's state)."""
+        if self.env is None:
+            raise ValueError("checkpoint: the level schedule is not attached to an env")
+        config = dict(groups=self.groups, mode=self.mode, curriculum=self.curriculum, lookback=self.lookback, seed=self.seed,
+                      n_agents=self.n_agents, n_slots=self.pool.n_slots)
+        scalars = dict(training_steps=self.training_steps, draws=self.draws, _fraction_sent=self._fraction_sent)
+        return config, scalars, {k: self.t[k] for k in self._CHECKPOINT_TENSORS}
+
     def stats(self):
         """Per group, read back now: ``episodes``, ``records`` (the ring's count, the first 0.0 included), ``best``
         (best_perf_lvl*), ``recent`` (recent<lookback>_perf_lvl*), ``probabilities`` (the device's in curriculum mode, else

@@ -1423,6 +1423,7 @@ class SafeLifeVectorEnv(object):
         if self._se is not None and self._se.get("last_done") is not None:
             self.side_effects_launch()
             self.torch.cuda.current_stream().wait_event(self._se["last_done"])
+            self._se["joined"] = self._se["last_done"]      # (what checkpoint.refuse_env asks about; the wait is made anyway)
 
     def side_effect_occupancy(self, env_ids, rng, num_samples=1000):
         """The two ``life_occupancy`` tensors of ``side_effect_score`` (side_effects.py:103-111) for the
@@ -1450,6 +1451,39 @@ class SafeLifeVectorEnv(object):
         occ0 = speedups.life_occupancy_batch(b1, prob, rng, num_samples)
         occ1 = speedups.life_occupancy_batch(b2, prob, rng, num_samples)
         return occ0, occ1, b0, b2
+
+    # ------------------------------------------------------------------ checkpoints (checkpoint.py)
+
+    _checkpoint_children = ("level_schedule", "episode_log", "episode_run", "episode_history")
+    #: rebuilt by the constructor from its arguments and the pool: not part of a checkpoint
+    _CHECKPOINT_DERIVED = ("pool_board", "pool_goals", "pool_exit_locs", "pool_rng", "points_table", "pool_ready",
+                           "score_lut", "move_table", "pool_baseline", "goal_cache")
+
+    def _checkpoint_state(self):
+        from . import checkpoint
+        checkpoint.refuse_env(self)
+        self._settle()
+        s, w = self.struct, self.struct.wrap
+        config = dict(num_envs=self.num_envs, env_offset=self.env_offset, time_limit=self.time_limit,
+                      auto_reset=self.auto_reset, board_shape=self.pool.shape, n_slots=self.pool.n_slots,
+                      exit_slots=self.pool.exit_slots, pool=checkpoint.pool_digest(self.pool), view_shape=self.view_shape,
+                      output_channels=self.output_channels, exit_points=s.exit_points,
+                      remove_white_goals=s.remove_white_goals, level_stride=s.level_stride, stream_salt=s.stream_salt,
+                      wrap_flags=w.flags, move_period=w.move_period, move_bonus=w.move_bonus, exit_bonus=w.exit_bonus,
+                      penalty_coef=w.penalty_coef, queue_capacity=None if self._se is None else self._se["capacity"])
+        tensors = {k: v for k, v in self.t.items() if k not in self._CHECKPOINT_DERIVED}
+        if self.obs is not None:
+            tensors["obs"] = self.obs
+        if self.policy_tensor is not None:
+            tensors["policy_tensor"] = self.policy_tensor
+        if self._se is not None:        # the finished-episode queue the step kernels are filling
+            for k, v in self._se["queue"][1].items():
+                tensors["queue_" + k] = v
+        return config, dict(steps_dispatched=self.steps_dispatched), tensors
+
+    def _checkpoint_loaded(self):
+        self.goal_cache_invalidate()        # (goals and the scalars' columns were written from outside the library)
+        self._caller_ahead = True
 
     # ------------------------------------------------------------------ host views
 
