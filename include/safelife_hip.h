@@ -1720,6 +1720,47 @@ int slhip_state_digest_prefix(const unsigned long long *bytes /* host */, int n_
 int slhip_state_digest(const sl_digest_segment *segments /* device */, int n_segments, unsigned long long salt,
                        unsigned long long *out /* device, n_segments */, void *workspace, void *stream);
 
+/* ---- batched pattern generation: N Metropolis chains of the level generator (additive again: two symbols, nothing existing
+ * changes; SL_ABI_VERSION stays where it is) ----------------------------------------------------------------------------------
+ * The reference's gen_pattern (gen_board.c:316-510) for N independent problems of one (H, W, depth), one wavefront each.
+ * Per problem p, all DEVICE memory:
+ *   layers     uint16 [N][depth][H][W]  layer 0 is the board; layer n is layer n - 1 after ONE step of the full Life rule at
+ *                                       spawn probability 0 (module.c:374-378 -- the caller makes them, with
+ *                                       slhip_advance_board, which also consumes the draws a spawner costs)
+ *   mask       int32  [N][H][W]         bits SL_GEN_NEW_CELL | SL_GEN_CAN_OSCILLATE | SL_GEN_INCLUDE_VIOLATIONS
+ *   seeds      int32  [N][H][W]         non-zero: a seed cell; NULL: the mask stands in (the reference's seeds=None)
+ *   params     double [N][12]           rel_max_iter, rel_min_fill, temperature, osc_bonus, cell_penalties[8] -- intercept and
+ *                                       slope per cell type EMPTY, WALL, ALIVE, TREE, as module.c:322-325 leaves them
+ *   rng        uint64 [N][6]            numpy PCG64: state hi, lo, inc hi, lo, has_uint32, uinteger; advanced IN PLACE.  The
+ *                                       32-bit draws of random_int buffer their high half in the last two words and the 64-bit
+ *                                       draws of random_float leave it alone, so four words do not carry this function.
+ *   out_board  uint16 [N][H][W]         the new layer 0 where status is 0, the input board otherwise
+ *   status     int32  [N]               0, SL_GEN_PATTERN_MAX_ITER, or SL_GEN_PATTERN_REFUSED (rel_max_iter * area * depth does
+ *                                       not fit an int: the reference's conversion is undefined there; nothing was drawn)
+ *   iterations int32  [N]               iterations run
+ * Board, status and the six words are bit-equal to the reference's.  All arithmetic is IEEE double without fusion; exp() is
+ * the one call whose last bit may differ from a host libm's, which changes a pick only when the uniform draw lands within a
+ * few ulps of a cumulative probability.
+ * Supported: 3 <= H, W <= 64 and 1 <= depth <= 4; anything else is refused (SL_E_SHAPE below 3x3 with the reference's message,
+ * SL_E_ARG for depth < 1, SL_E_UNSUPPORTED above the range).  A chain's state lives in LDS where it fits 64 KiB; for the larger
+ * shapes `workspace` is a 16-byte aligned device buffer of slhip_gen_pattern_workspace_bytes bytes (0: none needed, and
+ * `workspace` may be NULL).  Nothing outside a problem's own slices is read or written. */
+#define SL_GEN_NEW_CELL 1
+#define SL_GEN_CAN_OSCILLATE 2
+#define SL_GEN_INCLUDE_VIOLATIONS 4
+#define SL_GEN_PATTERN_MAX_SIDE 64
+#define SL_GEN_PATTERN_MAX_PERIOD 4
+#define SL_GEN_PATTERN_PARAMS 12
+#define SL_GEN_PATTERN_RNG_WORDS 6
+#define SL_GEN_PATTERN_MAX_ITER (-1)
+#define SL_GEN_PATTERN_REFUSED (-4)
+
+size_t slhip_gen_pattern_workspace_bytes(int N, int H, int W, int depth);
+
+int slhip_gen_pattern_batch(const uint16_t *layers, const int32_t *mask, const int32_t *seeds, const double *params,
+                            unsigned long long *rng, uint16_t *out_board, int32_t *status, int32_t *iterations, int N, int H,
+                            int W, int depth, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,7 +48,12 @@ EXPORTS = (
     "slhip_ppo_report_workspace_bytes", "slhip_ppo_report_rows", "slhip_ppo_report_finish",
     "slhip_dqn_workspace_bytes", "slhip_dqn_loss_forward", "slhip_dqn_loss_backward",
     "slhip_state_digest_workspace_bytes", "slhip_state_digest_prefix", "slhip_state_digest",
+    "slhip_gen_pattern_workspace_bytes", "slhip_gen_pattern_batch",
 )
+#: slhip_gen_pattern_batch: per-problem status, doubles per problem, generator words per problem, supported range
+GEN_PATTERN_MAX_ITER, GEN_PATTERN_REFUSED = -1, -4
+GEN_PATTERN_PARAMS, GEN_PATTERN_RNG_WORDS = 12, 6
+GEN_PATTERN_MAX_SIDE, GEN_PATTERN_MAX_PERIOD = 64, 4
 PPO_BAD_ACTION, PPO_BAD_INDEX = 1, 2
 #: sums_out of slhip_ppo_loss_forward: the doubles' names in order; slot PPO_SUM_LOSS_F32 holds a float32, not a double
 PPO_SUMS = ("policy", "value", "entropy", "entropy_term", "loss", "flag", "n")
@@ -450,6 +455,9 @@ def lib():
         L.slhip_state_digest_workspace_bytes.restype = C.c_size_t
         L.slhip_state_digest_prefix.argtypes = [_p, C.c_int, _p]
         L.slhip_state_digest.argtypes = [_p, C.c_int, C.c_ulonglong, _p, _p, _p]
+        L.slhip_gen_pattern_workspace_bytes.argtypes = [C.c_int] * 4
+        L.slhip_gen_pattern_workspace_bytes.restype = C.c_size_t
+        L.slhip_gen_pattern_batch.argtypes = [_p] * 8 + [C.c_int] * 4 + [_p, C.c_size_t, _p]
         L.slhip_obs_to_policy.argtypes = [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]
         L.slhip_gather_unique_id.argtypes = [_p]
         L.slhip_gather_init.argtypes = [_p, C.c_int, C.c_int, C.POINTER(_p)]

@@ -17,6 +17,7 @@
 #include <string.h>
 
 #include "sl_kernels.h"
+#include "sl_gen_pattern_core.h"
 
 namespace {
 
@@ -2298,6 +2299,28 @@ int slhip_state_digest(const sl_digest_segment *segments, int n_segments, unsign
         return fail(SL_E_ARG, "state_digest: segments / out / workspace not 8-byte aligned");
     const hipError_t err = sl::launch_state_digest(segments, n_segments, salt, out, workspace, (hipStream_t)stream);
     return err == hipSuccess ? SL_OK : hip_fail(err, "state_digest launch");
+}
+
+size_t slhip_gen_pattern_workspace_bytes(int N, int H, int W, int depth) {
+    return sl::gen_pattern_workspace_bytes(N, H, W, depth);
+}
+
+int slhip_gen_pattern_batch(const uint16_t *layers, const int32_t *mask, const int32_t *seeds, const double *params,
+                            unsigned long long *rng, uint16_t *out_board, int32_t *status, int32_t *iterations, int N, int H,
+                            int W, int depth, void *workspace, size_t workspace_bytes, void *stream) {
+    static_assert(SL_GEN_PATTERN_MAX_SIDE == sl::gp::MAX_SIDE && SL_GEN_PATTERN_MAX_PERIOD == sl::gp::MAX_DEPTH &&
+                  SL_GEN_PATTERN_PARAMS == sl::gp::N_PARAMS && SL_GEN_PATTERN_RNG_WORDS == sl::gp::N_RNG_WORDS &&
+                  SL_GEN_PATTERN_MAX_ITER == sl::gp::STATUS_MAX_ITER && SL_GEN_PATTERN_REFUSED == sl::gp::STATUS_REFUSED,
+                  "include/safelife_hip.h and sl_gen_pattern_core.h disagree");
+    const char *why = nullptr;
+    const int rc = sl::gp::validate(layers, mask, params, rng, out_board, status, iterations, N, H, W, depth, workspace,
+                                    workspace_bytes, &why);
+    if (rc != SL_OK) return fail(rc, why);
+    if (N == 0) return SL_OK;
+    const size_t need = sl::gp::workspace_bytes(N, H, W, depth);
+    const hipError_t err = sl::launch_gen_pattern(layers, mask, seeds, params, rng, out_board, status, iterations, N, H, W, depth,
+                                                  need ? workspace : nullptr, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "gen_pattern launch");
 }
 
 }  // extern "C"

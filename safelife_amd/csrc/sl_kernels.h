@@ -185,6 +185,11 @@ size_t digest_workspace_bytes(const unsigned long long *bytes, int n_segments);
 void digest_prefix(const unsigned long long *bytes, int n_segments, unsigned long long *prefix_out);
 hipError_t launch_state_digest(const sl_digest_segment *segments, int n_segments, unsigned long long salt,
                                unsigned long long *out, void *workspace, hipStream_t stream);
+// batched pattern generation (sl_gen_pattern.hip): n Metropolis chains of one (rows, cols, depth), one wavefront each
+size_t gen_pattern_workspace_bytes(int n, int rows, int cols, int depth);
+hipError_t launch_gen_pattern(const uint16_t *layers, const int32_t *mask, const int32_t *seeds, const double *params,
+                              unsigned long long *rng, uint16_t *out_board, int32_t *status, int32_t *iterations, int n,
+                              int rows, int cols, int depth, void *workspace, hipStream_t stream);
 // envs [e_first, e_first + e_count) of the batch; actions / reward_t / done_t are indexed [t * tstride + e]
 // with the env's index in the whole batch
 // (sl_aql.hip dispatches the same kernel from queues of the library's own: PreparedStep below)

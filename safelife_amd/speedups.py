@@ -23,8 +23,17 @@ are identical to the reference.  Only PCG64 (numpy's default) is supported.
 
 * ``_render_board(board, goals, sprites)``                    module.c:438-512
 
-Not provided (out of the hot path): gen_pattern,
-wrapped_label.
+* ``gen_pattern(board, mask, period, seeds=None, ...)``       module.c:252-417
+
+``gen_pattern`` is the level generator's Metropolis sampler (gen_board.c:316-510); ``gen_pattern_batch`` runs N
+independent problems of one (H, W, period) in one launch, one wavefront per chain.  It draws 32-bit integers as well as
+doubles, and numpy buffers the unused half of a 32-bit draw in the generator (``has_uint32`` / ``uinteger``), so this
+function carries SIX words per generator (``pcg64_words6`` / ``pcg64_set_words6``) where the others carry four.  With
+them the board, the exception and the generator's state afterwards equal the reference's, bit for bit.  It also provides
+the reference's exceptions: ``BoardGenException`` and, derived from it, ``MaxIterException``,
+``BadProbabilityException``, ``InsufficientAreaException``.
+
+Not provided: wrapped_label (generation never calls it; only stability_mask does).
 """
 import ctypes as C
 
@@ -90,6 +99,20 @@ def pcg64_set_words(bitgen, words):
     w = [int(x) for x in words]
     st["state"]["state"] = (w[0] << 64) | w[1]
     st["state"]["inc"] = (w[2] << 64) | w[3]
+    bitgen.state = st
+
+
+def pcg64_words6(bitgen):
+    """numpy PCG64 state -> uint64[6]: ``pcg64_words`` and the buffered half of a 32-bit draw (has_uint32, uinteger)."""
+    st = bitgen.state
+    return np.concatenate([pcg64_words(bitgen), np.array([st["has_uint32"], st["uinteger"]], dtype=np.uint64)])
+
+
+def pcg64_set_words6(bitgen, words):
+    w = [int(x) for x in words]
+    pcg64_set_words(bitgen, w[:4])
+    st = bitgen.state
+    st["has_uint32"], st["uinteger"] = w[4], w[5]
     bitgen.state = st
 
 
@@ -274,3 +297,168 @@ def _render_board(board, goals, sprites):
     if s.size != 70 * 70 * 4:
         raise ValueError("Sprites should have shape (70, 70, 4).")
     return render.render_board(b, g.reshape(b.shape), None, s)
+
+
+# --------------------------------------------------------------------------- pattern generation
+
+class BoardGenException(Exception):
+    """module.c:580-581"""
+
+
+class MaxIterException(BoardGenException):
+    pass
+
+
+class BadProbabilityException(BoardGenException):
+    pass
+
+
+class InsufficientAreaException(BoardGenException):
+    pass
+
+
+GEN_PATTERN_MAX_SIDE, GEN_PATTERN_MAX_PERIOD = _hip.GEN_PATTERN_MAX_SIDE, _hip.GEN_PATTERN_MAX_PERIOD
+
+
+def _pair(value, name):
+    try:
+        a, b = value
+        return float(a), float(b)
+    except (TypeError, ValueError):
+        raise TypeError("%s must be a pair of numbers: (penalty at density 0, penalty at density 1)" % name)
+
+
+def gen_pattern_params(max_iter=40, min_fill=0.2, temperature=0.5, osc_bonus=0.3, alive=(0, 0), wall=(100, 100),
+                       tree=(100, 100)):
+    """The keywords of ``gen_pattern`` -> float64 [12] as slhip_gen_pattern_batch takes them: rel_max_iter, rel_min_fill,
+    temperature, osc_bonus, then (intercept, slope) per cell type EMPTY, WALL, ALIVE, TREE.  A keyword is (penalty at
+    density 0, penalty at density 1); module.c:316-325 files ``alive`` under type 2, ``wall`` under 1, ``tree`` under 3 and
+    turns the second value into a slope."""
+    out = [float(max_iter), float(min_fill), float(temperature), float(osc_bonus), 0.0, 0.0]
+    for name, value in (("wall", wall), ("alive", alive), ("tree", tree)):
+        at0, at1 = _pair(value, name)
+        out += [at0, at1 - at0]
+    return np.array(out, dtype=np.float64)
+
+
+def _check_gen_range(H, W, period):
+    if period <= 0:
+        raise ValueError("Pattern period must be larger than 0.")
+    if H < 3 or W < 3:
+        raise ValueError("Board must be at least 3x3.")
+    if H > GEN_PATTERN_MAX_SIDE or W > GEN_PATTERN_MAX_SIDE or period > GEN_PATTERN_MAX_PERIOD:
+        raise ValueError("gen_pattern on the device supports boards from 3x3 to %dx%d and periods 1 to %d (got %dx%d, "
+                         "period %d)" % (GEN_PATTERN_MAX_SIDE, GEN_PATTERN_MAX_SIDE, GEN_PATTERN_MAX_PERIOD, H, W, period))
+
+
+def gen_pattern_batch(boards, masks, period, seeds=None, params=None, rng=None, out=None):
+    """N independent ``gen_pattern`` problems of one shape and period in one launch.
+
+    boards uint16 [N,H,W]; masks int32 [N,H,W]; seeds int32 [N,H,W] or None (the masks stand in); params float64 [N,12]
+    (``gen_pattern_params``; None: the defaults for every problem); rng uint64 [N,6] (``pcg64_words6``), advanced IN
+    PLACE.  All numpy arrays, or all torch tensors on the device (uint16 / uint64 travelling as int16 / int64).
+    Returns (boards, status, iterations) of the same kind: the new boards -- the input board where status is not 0 --,
+    status int32 [N] (0, -1 = max-iter, -4 = refused: max_iter * area * period does not fit an int) and the iterations
+    run int32 [N].  Raises nothing per problem.  ``out`` (device tensors only): caller-owned contiguous (boards int16
+    [N,H,W], status int32 [N], iterations int32 [N]) to write into."""
+    torch = _torch()
+    if rng is None:
+        raise ValueError("gen_pattern_batch needs the generators' words: rng uint64 [N,6]")
+    host = isinstance(boards, np.ndarray)
+    if boards.ndim != 3 or tuple(masks.shape) != tuple(boards.shape) or (seeds is not None
+                                                                          and tuple(seeds.shape) != tuple(boards.shape)):
+        raise ValueError("Board, mask, and seeds must all have the same shape.")
+    N, H, W = (int(x) for x in boards.shape)
+    period = int(period)
+    _check_gen_range(H, W, period)
+    if params is None:
+        params = np.tile(gen_pattern_params(), (N, 1))
+        if not host:
+            params = torch.from_numpy(params).to(boards.device)
+    if tuple(params.shape) != (N, _hip.GEN_PATTERN_PARAMS) or tuple(rng.shape) != (N, _hip.GEN_PATTERN_RNG_WORDS):
+        raise ValueError("params must be [N,12] and rng [N,6]")
+    if host:
+        if rng.dtype != np.uint64:
+            raise ValueError("rng must be uint64 [N,6]")
+        d_boards, d_masks = _to_device(boards, np.uint16), _to_device(masks, np.int32)
+        d_seeds = None if seeds is None else _to_device(seeds, np.int32)
+        d_params, d_rng = _to_device(params, np.float64), _to_device(rng, np.uint64)
+    else:
+        d_boards, d_masks, d_params, d_rng = boards.contiguous(), masks.contiguous(), params.contiguous(), rng.contiguous()
+        d_seeds = None if seeds is None else seeds.contiguous()
+        if (d_boards.dtype != torch.int16 or d_masks.dtype != torch.int32 or d_params.dtype != torch.float64
+                or d_rng.dtype != torch.int64 or (d_seeds is not None and d_seeds.dtype != torch.int32)):
+            raise ValueError("device tensors: boards int16, masks / seeds int32, params float64, rng int64")
+    dev = d_boards.device
+    if out is not None:
+        out, status, iters = out
+        if host or not (out.is_contiguous() and status.is_contiguous() and iters.is_contiguous()
+                        and out.dtype == torch.int16 and status.dtype == iters.dtype == torch.int32
+                        and tuple(out.shape) == (N, H, W) and tuple(status.shape) == tuple(iters.shape) == (N,)):
+            raise ValueError("out: contiguous device tensors (int16 [N,H,W], int32 [N], int32 [N]), with device inputs")
+    else:
+        out = torch.empty_like(d_boards)
+        status = torch.empty((N,), dtype=torch.int32, device=dev)
+        iters = torch.empty((N,), dtype=torch.int32, device=dev)
+    if N:
+        layers = [d_boards]
+        if period > 1:          # module.c:374-378: the later layers by the full rule at spawn_prob 0 -- spawners still draw
+            p0 = torch.zeros((N,), dtype=torch.float32, device=dev)
+            rng4 = d_rng[:, :4].contiguous()
+            for _ in range(1, period):
+                layers.append(advance_board_batch(layers[-1], p0, rng4, 1))
+            d_rng[:, :4] = rng4
+        d_layers = d_boards if period == 1 else torch.stack(layers, dim=1).contiguous()
+        need = _hip.lib().slhip_gen_pattern_workspace_bytes(N, H, W, period)
+        work = torch.empty((need,), dtype=torch.uint8, device=dev) if need else None
+        rc = _hip.lib().slhip_gen_pattern_batch(_hip.ptr(d_layers), _hip.ptr(d_masks), _hip.ptr(d_seeds), _hip.ptr(d_params),
+                                                _hip.ptr(d_rng), _hip.ptr(out), _hip.ptr(status), _hip.ptr(iters), N, H, W,
+                                                period, _hip.ptr(work), need, _hip.current_stream_ptr())
+        _hip.check(rc, "Board must be at least 3x3.")
+    if host:
+        np.copyto(rng, _to_host(d_rng, np.uint64))
+        return _to_host(out, np.uint16), _to_host(status, np.int32), _to_host(iters, np.int32)
+    if d_rng.data_ptr() != rng.data_ptr():
+        rng.copy_(d_rng)
+    return out, status, iters
+
+
+def _as_2d(obj, dtype, what):
+    try:
+        return np.array(obj).astype(dtype)          # NPY_ARRAY_ENSURECOPY | NPY_ARRAY_FORCECAST
+    except (TypeError, ValueError):
+        raise ValueError("Board and/or mask and/or seeds are not arrays.")
+
+
+def gen_pattern(board, mask, period, seeds=None, max_iter=40, min_fill=0.2, temperature=0.5, osc_bonus=0.3,
+                alive=(0, 0), wall=(100, 100), tree=(100, 100)):
+    """Generate a random (potentially oscillating) pattern in the part of `board` that `mask` opens (module.c:252-417):
+    returns the new board, uint16, the input untouched; raises MaxIterException when the sampler runs out of iterations.
+    Draws from the process-global generator, which ends where the reference's would."""
+    if isinstance(period, float) or not hasattr(period, "__index__"):
+        raise TypeError("period must be an integer")
+    period = int(period)
+    params = gen_pattern_params(max_iter, min_fill, temperature, osc_bonus, alive, wall, tree)
+    b = _as_2d(board, np.uint16, "board")
+    m = _as_2d(mask, np.int32, "mask")
+    s = None if seeds is None else _as_2d(seeds, np.int32, "seeds")
+    if period <= 0:
+        raise ValueError("Pattern period must be larger than 0.")
+    if b.ndim != 2 or m.ndim != 2 or (s is not None and s.ndim != 2):
+        raise ValueError("Board, mask, and seeds must all be dimension 2.")
+    if b.shape[0] < 3 or b.shape[1] < 3:
+        raise ValueError("Board must be at least 3x3.")
+    if b.shape != m.shape or (s is not None and s.shape != b.shape):
+        raise ValueError("Board, mask, and seeds must all have the same shape.")
+    _check_gen_range(b.shape[0], b.shape[1], period)
+    bitgen = _current_bitgen()
+    words = pcg64_words6(bitgen)[None].copy()
+    out, status, _ = gen_pattern_batch(b[None], m[None], period, None if s is None else s[None], params[None], words)
+    if status[0] == _hip.GEN_PATTERN_REFUSED:
+        raise ValueError("max_iter * area * period does not fit an int")
+    pcg64_set_words6(bitgen, words[0])
+    if status[0] == _hip.GEN_PATTERN_MAX_ITER:
+        raise MaxIterException("Max-iter hit. Aborting!")
+    if status[0] != 0:
+        raise BoardGenException("Miscellany error.")
+    return out[0]
