@@ -1761,6 +1761,38 @@ int slhip_gen_pattern_batch(const uint16_t *layers, const int32_t *mask, const i
                             unsigned long long *rng, uint16_t *out_board, int32_t *status, int32_t *iterations, int N, int H,
                             int W, int depth, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- batched region partition of the level generator (additive again: two symbols, nothing existing changes; SL_ABI_VERSION
+ * stays where it is) ---------------------------------------------------------------------------------------------------------------
+ * safelife_amd.proc_gen.partition for N independent problems of one (H, W), one wavefront each.  Per problem p, all DEVICE
+ * memory:
+ *   rng          uint64 [N][6]     numpy PCG64: state hi, lo, inc hi, lo, has_uint32, uinteger; advanced IN PLACE where status
+ *                                  is 0.  The draws are numpy's: Generator.integers(0, n) is Lemire's bounded method on
+ *                                  next_uint32 (the low half of a 64-bit output first, the high half buffered in the last two
+ *                                  words; nothing drawn for n == 1), Generator.random() a fresh 64-bit output.
+ *   min_regions  int32  [N]        the problem's bounds as the spec gives them; clamped as the host function clamps them:
+ *   max_regions  int32  [N]        lo = max(1, min), hi = max(max, lo)
+ *   labels       int16  [N][H][W]  0 = buffer, 1.. = region; written where status is 0
+ *   status       int32  [N]        0; SL_PARTITION_REFUSED: H or W outside 3 .. 64, or hi above `regions` -- nothing was drawn;
+ *                                  SL_PARTITION_CAPPED: the turn loop passed regions * H * W + 1 turns or a bounded draw 64
+ *                                  redraws (neither happens: the caps are there because no loop on a shared device may be
+ *                                  unbounded).  Where status is not 0 the problem's labels and words are left untouched.
+ * Labels and words are bit-equal to proc_gen.partition on a Generator(PCG64) set to the same words.
+ * `regions` (1 .. 8) is how many regions a problem's state has room for: one bitmap and one frontier of H * W cells per region
+ * beside the labels.  The state lives in LDS where it fits 64 KiB; above that (64x64 with room for eight) `workspace` is a
+ * 16-byte aligned device buffer of slhip_partition_workspace_bytes bytes (0: none needed, and `workspace` may be NULL).
+ * Errors of the call itself (SL_E_ARG): N < 0, regions outside 1 .. 8, a null or misaligned pointer, a workspace too small. */
+#define SL_PARTITION_MAX_SIDE 64
+#define SL_PARTITION_MAX_REGIONS 8
+#define SL_PARTITION_RNG_WORDS 6
+#define SL_PARTITION_REFUSED (-4)
+#define SL_PARTITION_CAPPED (-5)
+
+size_t slhip_partition_workspace_bytes(int N, int H, int W, int max_regions);
+
+int slhip_partition_batch(unsigned long long *rng, const int32_t *min_regions, const int32_t *max_regions, int16_t *labels,
+                          int32_t *status, int N, int H, int W, int regions, void *workspace, size_t workspace_bytes,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

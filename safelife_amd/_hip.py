@@ -49,7 +49,11 @@ EXPORTS = (
     "slhip_dqn_workspace_bytes", "slhip_dqn_loss_forward", "slhip_dqn_loss_backward",
     "slhip_state_digest_workspace_bytes", "slhip_state_digest_prefix", "slhip_state_digest",
     "slhip_gen_pattern_workspace_bytes", "slhip_gen_pattern_batch",
+    "slhip_partition_workspace_bytes", "slhip_partition_batch",
 )
+#: slhip_partition_batch: per-problem status, the supported range
+PARTITION_REFUSED, PARTITION_CAPPED = -4, -5
+PARTITION_MAX_SIDE, PARTITION_MAX_REGIONS = 64, 8
 #: slhip_gen_pattern_batch: per-problem status, doubles per problem, generator words per problem, supported range
 GEN_PATTERN_MAX_ITER, GEN_PATTERN_REFUSED = -1, -4
 GEN_PATTERN_PARAMS, GEN_PATTERN_RNG_WORDS = 12, 6
@@ -458,6 +462,9 @@ def lib():
         L.slhip_gen_pattern_workspace_bytes.argtypes = [C.c_int] * 4
         L.slhip_gen_pattern_workspace_bytes.restype = C.c_size_t
         L.slhip_gen_pattern_batch.argtypes = [_p] * 8 + [C.c_int] * 4 + [_p, C.c_size_t, _p]
+        L.slhip_partition_workspace_bytes.argtypes = [C.c_int] * 4
+        L.slhip_partition_workspace_bytes.restype = C.c_size_t
+        L.slhip_partition_batch.argtypes = [_p] * 5 + [C.c_int] * 4 + [_p, C.c_size_t, _p]
         L.slhip_obs_to_policy.argtypes = [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, _p]
         L.slhip_gather_unique_id.argtypes = [_p]
         L.slhip_gather_init.argtypes = [_p, C.c_int, C.c_int, C.POINTER(_p)]

@@ -18,6 +18,7 @@
 
 #include "sl_kernels.h"
 #include "sl_gen_pattern_core.h"
+#include "sl_partition_core.h"
 
 namespace {
 
@@ -2321,6 +2322,27 @@ int slhip_gen_pattern_batch(const uint16_t *layers, const int32_t *mask, const i
     const hipError_t err = sl::launch_gen_pattern(layers, mask, seeds, params, rng, out_board, status, iterations, N, H, W, depth,
                                                   need ? workspace : nullptr, (hipStream_t)stream);
     return err == hipSuccess ? SL_OK : hip_fail(err, "gen_pattern launch");
+}
+
+size_t slhip_partition_workspace_bytes(int N, int H, int W, int max_regions) {
+    return sl::partition_workspace_bytes(N, H, W, max_regions);
+}
+
+int slhip_partition_batch(unsigned long long *rng, const int32_t *min_regions, const int32_t *max_regions, int16_t *labels,
+                          int32_t *status, int N, int H, int W, int regions, void *workspace, size_t workspace_bytes,
+                          void *stream) {
+    static_assert(SL_PARTITION_MAX_SIDE == sl::pt::MAX_SIDE && SL_PARTITION_MAX_REGIONS == sl::pt::MAX_REGIONS &&
+                  SL_PARTITION_RNG_WORDS == sl::pt::N_RNG_WORDS && SL_PARTITION_REFUSED == sl::pt::STATUS_REFUSED &&
+                  SL_PARTITION_CAPPED == sl::pt::STATUS_CAPPED, "include/safelife_hip.h and sl_partition_core.h disagree");
+    const char *why = nullptr;
+    const size_t need = sl::pt::workspace_bytes(N, H, W, regions);
+    const int rc = sl::pt::validate(rng, min_regions, max_regions, labels, status, N, regions, need, workspace, workspace_bytes,
+                                    &why);
+    if (rc != SL_OK) return fail(rc, why);
+    if (N == 0) return SL_OK;
+    const hipError_t err = sl::launch_partition(rng, min_regions, max_regions, labels, status, N, H, W, regions,
+                                                need ? workspace : nullptr, (hipStream_t)stream);
+    return err == hipSuccess ? SL_OK : hip_fail(err, "partition launch");
 }
 
 }  // extern "C"

@@ -190,6 +190,10 @@ size_t gen_pattern_workspace_bytes(int n, int rows, int cols, int depth);
 hipError_t launch_gen_pattern(const uint16_t *layers, const int32_t *mask, const int32_t *seeds, const double *params,
                               unsigned long long *rng, uint16_t *out_board, int32_t *status, int32_t *iterations, int n,
                               int rows, int cols, int depth, void *workspace, hipStream_t stream);
+// batched region partition (sl_partition.hip): n partitions of one (rows, cols) with room for `regions` regions, one wavefront each
+size_t partition_workspace_bytes(int n, int rows, int cols, int regions);
+hipError_t launch_partition(unsigned long long *rng, const int32_t *min_regions, const int32_t *max_regions, int16_t *labels,
+                            int32_t *status, int n, int rows, int cols, int regions, void *workspace, hipStream_t stream);
 // envs [e_first, e_first + e_count) of the batch; actions / reward_t / done_t are indexed [t * tstride + e]
 // with the env's index in the whole batch
 // (sl_aql.hip dispatches the same kernel from queues of the library's own: PreparedStep below)

@@ -14,7 +14,10 @@ So a level is a GENERATOR FUNCTION: where it needs a pattern it yields a ``Patte
 and its own generator's six words) and is resumed with the answer; the retry ladder (min_fill x 0.94 on max-iter, max_fill x
 1.07 on an overfull pattern, ten retries) is simply more yields.  ``gen_games(params, seeds)`` drives N such coroutines and
 hands each round's pending requests to the backend in ONE call; the default backend groups them by (H, W, period) and runs
-``speedups.gen_pattern_batch``, one wavefront per chain.
+``speedups.gen_pattern_batch``, one wavefront per chain.  The region partition -- a scalar loop of a few hundred turns, most
+of the glue's time -- goes the same way: a level yields a ``PartitionRequest`` (its generator's six words, the shape, the
+bounds), a round's partition requests go to the ``partition_backend`` in one call, and the default one runs
+``speedups.partition_batch``, one wavefront per partition, bit-equal to ``partition`` below, which stays the reference.
 
 Two properties are the contract:
 
@@ -198,7 +201,15 @@ def partition(rng, shape, min_regions=2, max_regions=5, **_):
     return np.array(label, np.int16).reshape(H, W)
 
 
-# --------------------------------------------------------------------------- pattern requests
+# --------------------------------------------------------------------------- requests
+
+class PartitionRequest(object):
+    """The partition a level is waiting for: the level generator's six words, the board shape and the bounds as the spec
+    gives them (``partition`` clamps them).  The answer is ``(labels, words)``: int16 [H, W] and the words after."""
+
+    def __init__(self, words, shape, min_regions=2, max_regions=5):
+        self.words, self.shape, self.min_regions, self.max_regions = words, tuple(shape), min_regions, max_regions
+
 
 class PatternRequest(object):
     """One call of gen_pattern a level is waiting for: board uint16 [H, W], mask int32 [H, W], seeds int32 [H, W] or None,
@@ -411,12 +422,16 @@ def _place_agents(rng, board, regions, agents, agent_types):
 
 
 def level_coroutine(params, seed, name=None):
-    """One level as a generator: yields PatternRequests (send the answers back), returns the ``levels.Level``.  Every draw
-    comes from ``np.random.default_rng(seed)``."""
+    """One level as a generator: yields one PartitionRequest, then PatternRequests (send the answers back), returns the
+    ``levels.Level``.  Every draw comes from ``np.random.default_rng(seed)``."""
     rng = np.random.default_rng(seed)
     shape = tuple(int(x) for x in _resolve(params.get("board_shape", (25, 25)), rng))
     min_performance = float(_resolve(params.get("min_performance", -1), rng))
-    regions = partition(rng, shape, **(_resolve(params.get("partitioning") or {}, rng)))
+    bounds = _resolve(params.get("partitioning") or {}, rng)
+    regions, words = yield PartitionRequest(speedups.pcg64_words6(rng.bit_generator), shape, bounds.get("min_regions", 2),
+                                            bounds.get("max_regions", 5))
+    speedups.pcg64_set_words6(rng.bit_generator, words)
+    regions = np.array(regions, np.int16).reshape(shape)
     partition_map = regions.copy()
     board = np.zeros(shape, np.uint16)
     goals = np.zeros(shape, np.uint16)
@@ -468,6 +483,37 @@ def device_backend(requests):
     return answers
 
 
+def host_partition_backend(requests):
+    """``partition`` per request, on a generator set to the request's words."""
+    bitgen = np.random.PCG64(0)
+    answers = []
+    for rq in requests:
+        speedups.pcg64_set_words6(bitgen, rq.words)
+        labels = partition(np.random.Generator(bitgen), rq.shape, min_regions=rq.min_regions, max_regions=rq.max_regions)
+        answers.append((labels, speedups.pcg64_words6(bitgen)))
+    return answers
+
+
+def device_partition_backend(requests):
+    """All pending partitions in as few launches as there are board shapes: ``speedups.partition_batch``.  A problem the
+    device refuses (a shape or a number of regions outside its range) or caps is run on the host from the request's words."""
+    answers = [None] * len(requests)
+    groups = {}
+    for i, rq in enumerate(requests):
+        groups.setdefault(rq.shape, []).append(i)
+    for shape, idx in groups.items():
+        words = np.stack([requests[i].words for i in idx]).astype(np.uint64)
+        lo = np.array([int(requests[i].min_regions) for i in idx], np.int64)
+        hi = np.array([int(requests[i].max_regions) for i in idx], np.int64)
+        labels, after, status = speedups.partition_batch(words, shape, lo, hi)
+        for j, i in enumerate(idx):
+            if int(status[j]) == 0:
+                answers[i] = (labels[j], after[j].copy())
+            else:
+                answers[i] = host_partition_backend([requests[i]])[0]
+    return answers
+
+
 def function_backend(module):
     """A backend over any drop-in of the reference's native module (``gen_pattern``, ``set_bit_generator``,
     ``MaxIterException``, ``BoardGenException``): one call per request, on a generator set to the request's words."""
@@ -491,10 +537,14 @@ def function_backend(module):
     return backend
 
 
-def gen_games(params, seeds, backend=None, name="procgen"):
+def gen_games(params, seeds, backend=None, name="procgen", partition_backend=None):
     """N levels of the spec `params`, level k from ``seeds[k]`` alone.  Each round, the levels that wait for a pattern hand
-    their requests to `backend` in one call (default: ``device_backend``).  -> list of ``levels.Level`` with board, goals,
-    agent_locs, points_table, min_performance and name."""
+    their requests to `backend` in one call (default: ``device_backend``), and the levels that wait for their partition hand
+    theirs to `partition_backend` in one call (default: ``device_partition_backend`` where the patterns run on the device
+    too, ``host_partition_backend`` under an explicit `backend`).  -> list of ``levels.Level`` with board, goals, agent_locs,
+    points_table, min_performance and name."""
+    if partition_backend is None:
+        partition_backend = device_partition_backend if backend is None else host_partition_backend
     backend = backend or device_backend
     seeds = list(seeds)
     coros = [level_coroutine(params, s, name="%s-%s" % (name, s)) for s in seeds]
@@ -507,8 +557,13 @@ def gen_games(params, seeds, backend=None, name="procgen"):
             done[k] = stop.value
     while waiting:
         order = sorted(waiting)
-        answers = backend([waiting[k] for k in order])
-        for k, answer in zip(order, answers):
+        answers = {}
+        for kind, serve in ((PartitionRequest, partition_backend), (PatternRequest, backend)):
+            mine = [k for k in order if isinstance(waiting[k], kind)]
+            if mine:
+                answers.update(zip(mine, serve([waiting[k] for k in mine])))
+        for k in order:
+            answer = answers[k]
             try:
                 waiting[k] = coros[k].send(answer)
             except StopIteration as stop:
@@ -517,7 +572,7 @@ def gen_games(params, seeds, backend=None, name="procgen"):
     return done
 
 
-def fill_pool(pool, slots, params, seeds, backend=None, env=None):
+def fill_pool(pool, slots, params, seeds, backend=None, env=None, partition_backend=None):
     """Generate one level per logical slot of the refreshable ``LevelPool`` and hand them over as ``pool.prepare`` made
     them.  Without `env` they go into the host pool (``pool.replace``); with the ``SafeLifeVectorEnv`` that steps on the pool
     they are staged on the device (``env.pool_stage``, which does the replace), and the caller's ``env.pool_commit()`` makes
@@ -525,7 +580,7 @@ def fill_pool(pool, slots, params, seeds, backend=None, env=None):
     slots, seeds = list(slots), list(seeds)
     if len(slots) != len(seeds):
         raise ValueError("one seed per slot")
-    prepared = pool.prepare(gen_games(params, seeds, backend=backend))
+    prepared = pool.prepare(gen_games(params, seeds, backend=backend, partition_backend=partition_backend))
     if env is not None:
         if env.pool is not pool:
             raise ValueError("env steps on another pool")

@@ -33,6 +33,10 @@ them the board, the exception and the generator's state afterwards equal the ref
 the reference's exceptions: ``BoardGenException`` and, derived from it, ``MaxIterException``,
 ``BadProbabilityException``, ``InsufficientAreaException``.
 
+``partition_batch(words, shape, min_regions, max_regions)`` is the level generator's region partition
+(``proc_gen.partition``, this project's own) for N generators in one launch, one wavefront per partition, bit-equal to the
+host function: labels and the six words afterwards.
+
 Not provided: wrapped_label (generation never calls it; only stability_mask does).
 """
 import ctypes as C
@@ -462,3 +466,74 @@ def gen_pattern(board, mask, period, seeds=None, max_iter=40, min_fill=0.2, temp
     if status[0] != 0:
         raise BoardGenException("Miscellany error.")
     return out[0]
+
+
+# --------------------------------------------------------------------------- the level generator's region partition
+
+PARTITION_MAX_SIDE, PARTITION_MAX_REGIONS = _hip.PARTITION_MAX_SIDE, _hip.PARTITION_MAX_REGIONS
+
+
+def partition_batch(words, shape, min_regions=2, max_regions=5, out=None):
+    """N independent ``proc_gen.partition`` problems of one board shape in one launch.
+
+    words uint64 [N,6] (``pcg64_words6``; read only); shape (H, W); min_regions / max_regions: scalars or int32 [N].  All
+    numpy, or device tensors (words int64, bounds int32 or scalars).  Returns (labels int16 [N,H,W], words [N,6] afterwards,
+    status int32 [N]) of the same kind.  Where status is 0, labels and words are bit-equal to ``proc_gen.partition`` on a
+    Generator(PCG64) set to the problem's words.  Status -4: refused -- H or W outside 3 .. 64, or more than 8 regions after
+    the host function's clamping (lo = max(1, min), hi = max(max, lo)); -5: a loop cap ended the problem.  Where status is not
+    0 the labels are left as they were (zeros, or what ``out`` held) and the words are the input's: run the host function.
+    Raises nothing per problem.  ``out`` (device tensors only): caller-owned contiguous (labels int16 [N,H,W], words int64
+    [N,6], status int32 [N]) to write into."""
+    torch = _torch()
+    host = isinstance(words, np.ndarray)
+    H, W = (int(x) for x in shape)
+    if words.ndim != 2 or int(words.shape[1]) != 6:
+        raise ValueError("words must be [N,6]")
+    N = int(words.shape[0])
+    if host:
+        if words.dtype != np.uint64:
+            raise ValueError("words must be uint64 [N,6]")
+        d_in = _to_device(words, np.uint64)
+    else:
+        if words.dtype != torch.int64:
+            raise ValueError("device tensors: words int64 [N,6]")
+        d_in = words
+    dev = d_in.device
+
+    def bounds(value, name):
+        if isinstance(value, torch.Tensor):
+            t = value.to(device=dev, dtype=torch.int32).contiguous()
+        elif isinstance(value, np.ndarray) and value.ndim:
+            t = torch.from_numpy(np.ascontiguousarray(np.clip(value, -2 ** 31, 2 ** 31 - 1), dtype=np.int32)).to(dev)
+        else:
+            t = torch.full((N,), max(-2 ** 31, min(2 ** 31 - 1, int(value))), dtype=torch.int32, device=dev)
+        if tuple(t.shape) != (N,):
+            raise ValueError("%s must be a scalar or one value per problem" % name)
+        return t
+
+    d_lo, d_hi = bounds(min_regions, "min_regions"), bounds(max_regions, "max_regions")
+    if out is not None:
+        labels, d_words, status = out
+        if host or not (labels.is_contiguous() and d_words.is_contiguous() and status.is_contiguous()
+                        and labels.dtype == torch.int16 and d_words.dtype == torch.int64 and status.dtype == torch.int32
+                        and tuple(labels.shape) == (N, H, W) and tuple(d_words.shape) == (N, 6)
+                        and tuple(status.shape) == (N,)):
+            raise ValueError("out: contiguous device tensors (int16 [N,H,W], int64 [N,6], int32 [N]), with device inputs")
+        d_words.copy_(d_in)
+    else:
+        labels = torch.zeros((N, H, W), dtype=torch.int16, device=dev)
+        d_words = d_in if host else d_in.clone().contiguous()
+        status = torch.empty((N,), dtype=torch.int32, device=dev)
+    if N:
+        # room for as many regions as the largest clamped bound asks for, 8 at the most (the problems above are refused)
+        room = int(torch.maximum(d_hi, d_lo.clamp(min=1)).max())
+        room = max(1, min(PARTITION_MAX_REGIONS, room))
+        need = _hip.lib().slhip_partition_workspace_bytes(N, H, W, room)
+        work = torch.empty((need,), dtype=torch.uint8, device=dev) if need else None
+        rc = _hip.lib().slhip_partition_batch(_hip.ptr(d_words), _hip.ptr(d_lo), _hip.ptr(d_hi), _hip.ptr(labels),
+                                              _hip.ptr(status), N, H, W, room, _hip.ptr(work), need,
+                                              _hip.current_stream_ptr())
+        _hip.check(rc)
+    if host:
+        return _to_host(labels, np.int16), _to_host(d_words, np.uint64), _to_host(status, np.int32)
+    return labels, d_words, status
