@@ -1309,21 +1309,77 @@ __device__ __forceinline__ void load_span(const u16 *__restrict__ src, unsigned 
 // produced WRONG boards now and then under concurrent launches in round 2 -- 64x64 spawner levels, ~1 run in 3.)
 __device__ __forceinline__ void store16(u32x4 *p, u32x4 v) { __builtin_nontemporal_store(v, p); }
 
+// A span leaves LDS in two halves: the lane's ds_reads first, all of a group and unconditionally (a slot beyond the
+// span is clamped to the span's last one: an in-bounds LDS read costs nothing and cannot fault), then ONE wait, then
+// the stores under the span's masks.  Written as `if (slot < nv) store16(.., s[slot])` every chunk became an
+// exec-masked block of its own -- ds_read_b128, s_waitcnt lgkmcnt(0), global_store_dwordx4 -- and the compiler moves no
+// LDS read across the branch of the block before it: three LDS round trips one after another at 25x25, eight at
+// 64x64, a fourth / ninth for the leftover cells.  A lane holds at most GRP = 4 chunks at a time (16 registers: the
+// row registers are dead by then); the wide shapes go in NGRP groups.
+template <int H, int W>
+struct SpanOut {
+    using Gm = Geom<H, W>;
+    static constexpr int NV_MAX = Gm::SPAN / 16;
+    static constexpr int NVI = (NV_MAX + 64 * WAVES - 1) / (64 * WAVES);
+    static constexpr int GRP = NVI < 4 ? NVI : 4;
+    static constexpr int NGRP = (NVI + GRP - 1) / GRP;
+    u32x4 c[GRP];
+    u32 cell;           // the lane's leftover cell (tail workgroup only), read with group 0
+
+    __device__ __forceinline__ void fetch(const unsigned char *region, int nbb, int tid, int grp) {
+        const u32x4 *s = (const u32x4 *)(region + Gm::PAD);
+#pragma unroll
+        for (int j = 0; j < GRP; ++j) {
+            const int i = grp * GRP + j;
+            if (i >= NVI) continue;
+            int slot = tid + 64 * WAVES * i;
+            if (64 * WAVES * (i + 1) > NV_MAX) slot = min(slot, NV_MAX - 1);
+            c[j] = s[slot];
+        }
+        // (nv * 8 + 7 cells end inside the region's trailing pad at the latest)
+        if (grp == 0) cell = ((const u16 *)s)[((nbb * Gm::HW * 2) >> 4) * 8 + (tid & 7)];
+    }
+    // the one wait.  (Opaque: left alone the compiler sinks each read back into the masked block of its store.)
+    __device__ __forceinline__ void land(int grp) {
+#pragma unroll
+        for (int j = GRP - 1; j >= 0; --j)
+            if (grp * GRP + j < NVI) asm volatile("" : "+v"(c[j]));
+        if (grp == 0) asm volatile("" : "+v"(cell));
+    }
+    __device__ __forceinline__ void store(u16 *__restrict__ dst, int nbb, int tid, int grp) const {
+        const int bytes = nbb * Gm::HW * 2;
+        const int nv = bytes >> 4;
+        u32x4 *d = (u32x4 *)dst;
+#pragma unroll
+        for (int j = 0; j < GRP; ++j) {
+            const int i = grp * GRP + j;
+            if (i >= NVI) continue;
+            const int slot = tid + 64 * WAVES * i;
+            if (slot < nv) store16(d + Gm::swz_chunk(slot), c[j]);
+        }
+        if (grp == NGRP - 1) {
+            const int rem = (bytes & 15) >> 1;
+            if (tid < rem) dst[nv * 8 + tid] = (u16)cell;
+        }
+    }
+    // the whole span, group by group.  AHEAD: the caller has fetched group 0, in a batch with other reads of its own
+    template <bool AHEAD>
+    __device__ __forceinline__ void run(u16 *__restrict__ dst, const unsigned char *region, int nbb, int tid) {
+#pragma unroll
+        for (int grp = 0; grp < NGRP; ++grp) {
+            if (!AHEAD || grp > 0) {
+                fetch(region, nbb, tid, grp);
+                land(grp);
+            }
+            store(dst, nbb, tid, grp);
+        }
+    }
+};
+
 template <int H, int W>
 __device__ __forceinline__ void store_span(u16 *__restrict__ dst, const unsigned char *region, int nbb, int tid) {
-    using Gm = Geom<H, W>;
-    const int bytes = nbb * Gm::HW * 2;
-    const int nv = bytes >> 4;
-    u32x4 *d = (u32x4 *)dst;
-    const u32x4 *s = (const u32x4 *)(region + Gm::PAD);
-    constexpr int NVI = (Gm::SPAN / 16 + 64 * WAVES - 1) / (64 * WAVES);
-#pragma unroll
-    for (int i = 0; i < NVI; ++i) {
-        const int slot = tid + 64 * WAVES * i;
-        if (slot < nv) store16(d + Gm::swz_chunk(slot), s[slot]);
-    }
-    const int rem = (bytes & 15) >> 1;
-    if (tid < rem) dst[nv * 8 + tid] = ((const u16 *)s)[nv * 8 + tid];
+    SpanOut<H, W> sp;
+    sp.template run<false>(dst, region, nbb, tid);
 }
 
 // ---- advance_board --------------------------------------------------------------------------------
@@ -2810,8 +2866,8 @@ __global__ __launch_bounds__(64 * WAVES,
     // level -- is carried out behind the NEXT workgroup barrier: the one at the top of the following step, or the
     // one in front of the final stores.
     bool any_reset = false;             // (wave-uniform) some board of the workgroup loaded a level in this launch
-    auto hand_over_block = [&]() {
-        const int any = box[0].any;
+    // any: box[0].any, as the caller read it behind the barrier; behind(): what the caller runs behind a reload's last barrier
+    auto hand_over_block = [&](const int any, auto &&behind) {
         if (any & 1) any_reset = true;
         if ((!LEAN || Gm::WAVES_PER_SIMD < 4) && (any & 2)) {
             // the step that ended an episode queued it for the side-effect pass (include/safelife_hip.h): the board
@@ -2976,14 +3032,78 @@ __global__ __launch_bounds__(64 * WAVES,
             *lrec = rec;
         }
         wg_sync();
+        behind();
     };
 
-    for (int t = 0;; ++t) {
-        if (t > 0) {
-            wg_sync();                             // the leaders' requests of the step before; after the last
-            if (hand_over) hand_over_block();            // step also the barrier in front of the stores
+    // The epilogue's LDS reads, behind the end barrier: ONE batch and one wait.  Everything a wave takes out of LDS on its
+    // way to s_endpgm -- the hand-over word, the goals' dirty flag, its generator words, the records' copy (stored by the
+    // leader wave), the boards' goals_static as the goal-word cache asks for them, the first group of the board span's
+    // chunks -- is asked for here, from clamped indices by every lane, and waited for once.  One after another, each
+    // read waited for in front of its own branch or store, they were five LDS round trips for a row wave and seven for
+    // the leader wave between the end barrier and s_endpgm.  A workgroup that goes through the hand-over block's reload
+    // fetches again behind it: the block rewrites image, generator words and records.
+    SpanOut<H, W> ep_img;
+    constexpr int REC_IT = (Gm::NB * 4 + 63) / 64;
+    u32x4 ep_rec[REC_IT];
+    u64 ep_rng = 0, ep_irng = 0;
+    int ep_any = 0, ep_dirty = 0, ep_gstat = 1;
+    constexpr int WST_WORDS = (int)(sizeof(sl_wrap_state) / 4), WST_IT = WRAP ? (Gm::NB * WST_WORDS + 64 * WAVES - 1) / (64 * WAVES) : 1;
+    u32 ep_wst[WST_IT] = {};        // (WRAP) the wrappers' state words
+    // (an opaque copy of the thread index: the stores' per-lane addresses are formed HERE -- left alone the compiler
+    //  hoists them above the step loop, where a handful of live 64-bit pointers tips the variants that sit at the
+    //  register limit into scratch; a kernel that uses scratch at all costs ~3 us more per launch)
+    int tid2 = tid, lane2 = lane, wave2 = tid >> 6;
+    // (What orders the batch is hipcc's placement of s_waitcnt around the empty asm statements below, as ROCm 7.2 does it:
+    //  after a toolchain change, compare the epilogue with profiles/step_epilogue_isa.txt again.)
+    static_assert(Gm::NB <= 64, "lane q of a wave looks at board q: the leaders, the records' copy and the goal-word cache's ballot");
+    // EP_PLAIN: the T-step kernels with observation of the spawner-free shapes up to 12x12 keep the epilogue as it was --
+    // hand-over behind the loop's own barrier, every value read where it is stored.  With the batch's control flow three
+    // of them (10x10 with and without the LDS score table, 12x12 with wrappers) declared a 36-byte private segment
+    // where they had 0, 0 and 28 bytes: an SGPR spill slot left in the frame.  This form leaves all twelve at or below
+    // what they had.
+    constexpr bool EP_PLAIN = !ONE && !LEAN && !SPAWN && H <= 12;
+    auto epilogue_fetch = [&]() {
+        tid2 = tid;
+        asm volatile("" : "+v"(tid2));
+        lane2 = tid2 & 63;
+        wave2 = tid2 >> 6;
+        if constexpr (EP_PLAIN) return;
+        ep_any = box[0].any;
+        if constexpr (!NOGOALS) ep_dirty = *dirty_flag;
+        if constexpr (GCACHE) ep_gstat = box[min(lane2, Gm::NB - 1)].gstat;
+        ep_rng = ((const u64 *)(smem_hi + Gm::OFF_RNG) + 4 * Gm::G * wave2)[min(lane2, 4 * Gm::G - 1)];
+        if (WRAP && inaction && T > 0)
+            ep_irng = ((const u64 *)(smem_hi + OFF_INB + Gm::REGION) + 4 * Gm::G * wave2)[min(lane2, 4 * Gm::G - 1)];
+#pragma unroll
+        for (int k = 0; k < REC_IT; ++k)
+            ep_rec[k] = ((const u32x4 *)(smem_hi + Gm::OFF_REC))[min(lane2 + 64 * k, Gm::NB * 4 - 1)];
+        if constexpr (WRAP) {
+#pragma unroll
+            for (int k = 0; k < WST_IT; ++k) ep_wst[k] = ((const u32 *)wst)[min(tid2 + 64 * WAVES * k, Gm::NB * WST_WORDS - 1)];
         }
-        if (t >= T) break;
+        ep_img.fetch(board, nbb, tid2, 0);
+        ep_img.land(0);             // (the youngest reads first: the one wait is theirs)
+        if constexpr (WRAP) {
+#pragma unroll
+            for (int k = WST_IT - 1; k >= 0; --k) asm volatile("" : "+v"(ep_wst[k]));
+        }
+#pragma unroll
+        for (int k = REC_IT - 1; k >= 0; --k) asm volatile("" : "+v"(ep_rec[k]));
+        if (WRAP) asm volatile("" : "+v"(ep_irng));
+        asm volatile("" : "+v"(ep_rng));
+        if constexpr (GCACHE) asm volatile("" : "+v"(ep_gstat));
+        // (the hand-over word too: its first use is the branch behind the batch -- left alone the compiler looks at it
+        //  as soon as it is in, with a wait of its own in front of the other reads)
+        asm volatile("" : "+v"(ep_any));
+        ep_any = __builtin_amdgcn_readfirstlane(ep_any);        // (one word for the workgroup: the branch stays a scalar one)
+    };
+
+    for (int t = 0; EP_PLAIN || t < T; ++t) {
+        if (t > 0) {
+            wg_sync();                             // the leaders' requests of the step before (EP_PLAIN: and of the last)
+            if (hand_over) hand_over_block(box[0].any, [] {});
+        }
+        if (EP_PLAIN && t >= T) break;
         if (WRAP && (env.wrap.flags & SL_WRAP_SIDE_EFFECT) && !inaction) {
             // baseline row (level, r) of every lane -> LDS, asynchronously; read after the CA pass
             // ("inaction": the env's own baseline instead, advanced and laid out by this kernel's third CA pass)
@@ -3170,6 +3290,12 @@ __global__ __launch_bounds__(64 * WAVES,
                 const bool ended = done && active;      // this step ends the episode
                 lrec->agent_row = ly;
                 lrec->agent_col = lx;
+                // (the record is COMPLETED here: goals_static arrives in the mailbox with the score, and a board that has
+                //  stepped is loaded -- behind the end barrier the two cost the leader wave an LDS read, a wait and an
+                //  LDS write in front of the records' copy; a reload writes its record whole, with the 0 the rows then
+                //  put into the mailbox)
+                lrec->goals_static = box[lq].gstat;
+                lrec->loaded = 1;
                 lrec->num_steps = steps;
                 lrec->episode_reward = ep_rew;
                 lrec->episode_length = ep_len;
@@ -3271,40 +3397,41 @@ __global__ __launch_bounds__(64 * WAVES,
                 box[lq].qslot = -1;
             }
         }
-        wg_sync();
-        hand_over_block();
     } else if (T == 0) {
+        if (lead) lrec->loaded = 1;                 // (an observation launch: the one thing it changes in a record)
+    }
+    // The end barrier: the leaders' requests of the last step (or of the reset launch) and their records are in LDS.
+    // The records are complete: the leaders' section finishes the record of a board that stepped, the reload block
+    // writes the one it loads whole, and a launch that does neither leaves agent location and goals_static as they came.
+    if constexpr (EP_PLAIN) {           // (the loop has taken the barrier and the hand-over of a launch that stepped)
+        if (T <= 0) wg_sync();
+        if (T < 0) hand_over_block(box[0].any, [] {});
+        epilogue_fetch();
+    } else {
         wg_sync();
+        epilogue_fetch();
+        // (a reload rewrites image, generator words and records: the batch is fetched AGAIN behind its last barrier, and
+        //  nothing of the first one lives across the block)
+        if (T != 0 && (hand_over || T < 0) && (ep_any & 3)) hand_over_block(ep_any, epilogue_fetch);
     }
     SL_STAMP(7);
-    // write-back of the records: the leaders complete their LDS copies, the leader wave stores them
+    // write-back of the records, by the leader wave
     if (lwave) {
-        if (lead) {
-            lrec->agent_row = ly;
-            lrec->agent_col = lx;
-            lrec->goals_static = box[lq].gstat;
-            if (T >= 0) lrec->loaded = 1;           // (a reset launch marks the envs it loads, above)
-        }
-        wave_sync();
-        int lane3 = lane;
-        asm volatile("" : "+v"(lane3));
-        for (int i = lane3; i < nbb * 4; i += 64)
-            ((u32x4 *)(env.scalars + e0b))[i] = ((const u32x4 *)(smem_hi + Gm::OFF_REC))[i];
+#pragma unroll
+        for (int k = 0; k < REC_IT; ++k)
+            if (lane2 + 64 * k < nbb * 4)
+                ((u32x4 *)(env.scalars + e0b))[lane2 + 64 * k] =
+                    EP_PLAIN ? ((const u32x4 *)(smem_hi + Gm::OFF_REC))[lane2 + 64 * k] : ep_rec[k];
     }
-    const int dirty = *dirty_flag;
+    const int dirty = EP_PLAIN ? *dirty_flag : ep_dirty;
     SL_STAMP(8);
-    // (an opaque copy of the thread index: the stores' per-lane addresses are formed HERE -- left alone the compiler
-    //  hoists them above the step loop, where a handful of live 64-bit pointers tips the variants that sit at the
-    //  register limit into scratch; a kernel that uses scratch at all costs ~3 us more per launch)
-    int tid2 = tid;
-    asm volatile("" : "+v"(tid2));
-    const int lane2 = tid2 & 63, wave2 = tid2 >> 6;
     // (round 3, measured and dropped: single-step launches storing only the boards the CA changed -- in a level of still
     //  lifes 57 % of the boards of a step are untouched apart from the agent's own cells, which the leaders then store
     //  themselves -- i.e. half the write traffic and half the dirty lines at the kernel boundary.  Bit-exact, and no
     //  faster: 8.01-8.09 against 7.91 us per two-slice C3 step in one session, re-measured in round 6 7.30-7.34 against
     //  6.65-6.68: the per-chunk test and 14 more registers cost what the bytes save)
-    store_span<H, W>(env.board + (size_t)e0b * HW, board, nbb, tid2);
+    if constexpr (EP_PLAIN) store_span<H, W>(env.board + (size_t)e0b * HW, board, nbb, tid2);
+    else ep_img.template run<true>(env.board + (size_t)e0b * HW, board, nbb, tid2);      // (group 0 came with the batch)
     if (dirty && !NOGOALS) store_span<H, W>(env.goals + (size_t)e0b * HW, goals, nbb, tid2);
     if (GCACHE && gc_flag && T != 0) {
         // GoalCache: a launch that had the goal span keeps the lanes' words if every board of the workgroup ends it with
@@ -3312,10 +3439,10 @@ __global__ __launch_bounds__(64 * WAVES,
         // launch that ran on cached words lowers the flag if one of its boards took a new level.
         bool all_static = !any_reset;
         if (!goals_free) {
-            all_static = true;
-#pragma unroll
-            for (int q = 0; q < Gm::NB; ++q)
-                if (q < nbb && box[q].gstat != 1) all_static = false;
+            // (lane q looks at board q, the word came with the epilogue's batch: one after another the boards were eight
+            //  LDS round trips at 25x25, in the workgroups a launch waits for anyway -- first steps after a reset, the
+            //  step after a reload)
+            all_static = __ballot(lane2 < nbb && ep_gstat != 1) == 0;
             if (all_static && live && (nbb == Gm::NB || e0b + nbb >= env.B)) {
 #pragma unroll
                 for (int c = 0; c < Gc::X4; ++c)
@@ -3333,15 +3460,19 @@ __global__ __launch_bounds__(64 * WAVES,
         }
     }
     if (lane2 < 4 * Gm::G && wave2 * Gm::G + (lane2 >> 2) < nbb)
-        ((u64 *)(env.rng + e0b + wave2 * Gm::G))[lane2] = ((const u64 *)(smem_hi + Gm::OFF_RNG) + 4 * Gm::G * wave2)[lane2];
-    if (WRAP)       // (10-row boards: 24 per workgroup, more state words than threads)
-        for (int i = tid2; i < nbb * (int)(sizeof(sl_wrap_state) / 4); i += 64 * WAVES)
-            ((u32 *)(env.wrap.state + e0b))[i] = ((const u32 *)wst)[i];
+        ((u64 *)(env.rng + e0b + wave2 * Gm::G))[lane2] =
+            EP_PLAIN ? ((const u64 *)(smem_hi + Gm::OFF_RNG) + 4 * Gm::G * wave2)[lane2] : ep_rng;
+    if (WRAP) {     // (10-row boards: 24 per workgroup, more state words than threads)
+#pragma unroll
+        for (int k = 0; k < WST_IT; ++k)
+            if (tid2 + 64 * WAVES * k < nbb * WST_WORDS)
+                ((u32 *)(env.wrap.state + e0b))[tid2 + 64 * WAVES * k] = EP_PLAIN ? ((const u32 *)wst)[tid2 + 64 * WAVES * k] : ep_wst[k];
+    }
     if (WRAP && inaction && T > 0) {
         store_span<H, W>(env.wrap.inaction_board + (size_t)e0b * HW, inb, nbb, tid2);
         if (lane2 < 4 * Gm::G && wave2 * Gm::G + (lane2 >> 2) < nbb)
             ((u64 *)(env.wrap.inaction_rng + e0b + wave2 * Gm::G))[lane2] =
-                ((const u64 *)(smem_hi + OFF_INB + Gm::REGION) + 4 * Gm::G * wave2)[lane2];
+                EP_PLAIN ? ((const u64 *)(smem_hi + OFF_INB + Gm::REGION) + 4 * Gm::G * wave2)[lane2] : ep_irng;
     }
 
     SL_STAMP(9);
